@@ -11,14 +11,21 @@ Workload (BASELINE.json configs[1]): 9-block ResnetGenerator + 3-layer PatchGAN 
 (weak scaling: global batch = 32 x N), synthetic U[-1,1) images, labels in {0,2}, seeded-random
 "pretrained" E/IP weights (no checkpoints ship offline).
 
-One JSON line on rank 0: value = whole-job images/s; `roofline` = the three kernels of the 256->256 3x3 residual
-convolution (forward, data gradient, weight gradient INCLUDING its reduce launch; 36 launches each per step;
+One JSON line on rank 0: value = whole-job images/s over the --steps timed steps, ms_per_step = wall time of one timed step.
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs if given, print the line.
+
+--dump-outputs DIR writes what the last timed step computed (fake_B, rec_A, every loss, a fixed seeded sample of the updated state
+of G, D and E) as DIR/<name>.npy; inputs and weights are seeded, so two builds can be compared output for output.
+
+--full adds the measurements the headline does not need.  `roofline` = the three kernels of the 256->256
+3x3 residual convolution (forward, data gradient, weight gradient INCLUDING its reduce launch; 36 launches each per step;
 fp32 contraction as two scaled fp16 pieces / three products on the f16 matrix pipe by default): every launch inside the timed
 region is bracketed by HIP events on its launch stream inside the library (pcgan_timer_*), the slowest of the three is the
 dominant kernel the top-level fields describe.  The step runs on several streams (parameter gradients, branches of backward_G, the
 next step's encoder passes and first generator pass beside the previous step's backward_D), so an in-region duration is that of a
 kernel SHARING the GPU; `ms_per_launch_alone` / `frac_alone` are the same launches with those streams off (3 extra steps after the
-region).  `cpu_baseline` = the oracle's PyTorch-CPU step on this host's cores, bounded sample.
+region).  Also the host issue time per step, the same steps on the two other convolution routes (`route_*`), per-rank diagnostics
+and the replica check of a multi-GPU run, and `cpu_baseline` = the oracle's PyTorch-CPU step on this host's cores, bounded sample.
 `python bench.py --dtype bf16` is the same line for BASELINE configs[2] per GPU (bf16 activations).
 """
 import argparse
@@ -108,6 +115,31 @@ def synthetic_batch(batch, size, rank, it=0):
     B = torch.rand(batch, 3, size, size, generator=g) * 2 - 1
     label = torch.randint(0, 2, (batch,), generator=g) * 2
     return {'A': A, 'B': B, 'label': label, 'A_paths': [''] * batch, 'B_paths': [''] * batch}
+
+
+STATE_SAMPLE = 1 << 20           # --dump-outputs: elements kept of each network's state (G alone has 11.4 M): ~25 MB written in all
+
+
+def dump_outputs(model, losses, out_dir):
+    """What the last step hands its caller, as .npy files under out_dir: the generator's two outputs (fake_B, rec_A; float32), every
+    loss (float64 scalars) and, per trained or running-statistics-carrying network (G, D, E), a fixed seeded sample of its state after
+    the step (floating-point state_dict entries in order, flattened; float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    model.sync_parameter_updates()
+    torch.cuda.synchronize()
+    for name in ('fake_B', 'rec_A'):
+        np.save(os.path.join(out_dir, name + '.npy'), getattr(model, name).detach().cpu().float().numpy())
+    for name, v in losses.items():
+        np.save(os.path.join(out_dir, 'loss_%s.npy' % name), np.float64(v))
+    for name in ('G', 'D', 'E'):
+        net = getattr(model, 'net' + name)
+        state = getattr(net, 'module', net).state_dict().values()
+        flat = torch.cat([t.detach().cpu().float().reshape(-1) for t in state if t.is_floating_point()])
+        if flat.numel() > STATE_SAMPLE:
+            pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:STATE_SAMPLE]
+            flat = flat[pick.sort().values]
+        np.save(os.path.join(out_dir, name + '_state_sample.npy'), flat.numpy())
 
 
 RES_CONV_KEY = (PER_GPU_BATCH, 256, 32, 32, 256, 3, 3, 1, 1, 1)   # the residual-block convolution: 36 forward launches per step
@@ -211,105 +243,10 @@ def cpu_baseline(batch=8, sweep_batch=4, final_steps=3, sweep_budget_s=45.0):
                           len(times), batch, len(sweep), sweep_batch, sweep_budget_s, best, time.perf_counter() - t_begin)}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'],
-                    help='activation storage type; the headline (BASELINE configs[1]) is fp32, bf16 is BASELINE configs[2] per GPU')
-    ap.add_argument('--resident-inputs', action='store_true',
-                    help='A/B only: keep the synthetic batches in HBM (no upload inside the timed region); the headline uploads them')
-    ap.add_argument('--no-experiment', action='store_true',
-                    help='skip the extra (not headline) run with the residual convolutions routed back to the fp32 MFMA kernels')
-    args = ap.parse_args()
-
-    # stdout carries the ONE JSON line and nothing else: native libraries write to file descriptor 1 behind Python's back (RCCL prints
-    # a five-line version banner on rank 0's stdout when its communicator comes up -- seen on the first RCCL run, round 4), so the
-    # descriptor itself points at stderr until the line is printed
-    sys.stdout.flush()
-    json_fd = os.dup(1)
-    os.dup2(2, 1)
-
-    from pcgan_amd.hip import parallel
-    world, rank, local = parallel.init_process_group()
-    assert world == args.gpus, 'launch with torchrun --nproc-per-node %d (WORLD_SIZE=%d)' % (args.gpus, world)
-    assert torch.cuda.is_available(), 'bench.py needs an MI355X (no CPU fallback)'
-    dev_index = local % torch.cuda.device_count()   # (one GPU per rank on a real node; a 1-GPU box can only rehearse)
-    torch.cuda.set_device(dev_index)
-    device = torch.device('cuda', dev_index)
-
-    tmpdir = tempfile.mkdtemp(prefix='pcgan_bench_')
-    with contextlib.redirect_stdout(sys.stderr):      # the reference's 'initialize network with ...' notices: stdout carries the JSON line only
-        model, opt = build_model(dev_index, PER_GPU_BATCH, SIZE, tmpdir, dtype=args.dtype)
-    # N_BATCHES distinct batches in PINNED host memory: set_input uploads them INSIDE the timed region (BaseModel.to_act: async copy on
-    # the upload stream, 2 x 6.3 MB + the labels per step -- SURVEY 8(a2) is part of the step; round 3 parked two batches in HBM)
-    batches = [synthetic_batch(PER_GPU_BATCH, SIZE, rank, it) for it in range(N_BATCHES)]
-    batches = [{k: (v.pin_memory() if isinstance(v, torch.Tensor) else v) for k, v in b.items()} for b in batches]
-    if args.resident_inputs:      # A/B only (round 3's form): batches parked in HBM before the region, declared ready by their producer
-        from pcgan_amd.hip import ops as _ops
-        batches = [{k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in b.items()} for b in batches]
-        torch.cuda.synchronize()
-        for b in batches:
-            _ops.mark_ready(b['A'])
-            _ops.mark_ready(b['B'])
-
-    def step(i):
-        model.set_input(batches[i % N_BATCHES])
-        model.optimize_parameters()
-
+def full_measurements(args, model, step, world, rank, value, t_issued):
+    """--full: every field beyond the headline (module docstring), measured after the timed steps (the in-region kernel timings were
+    recorded during them).  Runs on every rank -- the extra steps hold collectives -- and returns the fields on rank 0, None elsewhere."""
     from pcgan_amd.hip import ops
-    _progress('model built, warm-up')
-    for i in range(args.warmup):
-        step(i)
-    dist_on = parallel.is_distributed()     # more than one rank, or the one-rank RCCL rehearsal (PCGAN_FORCE_COLLECTIVES=1)
-    _progress('timed region')
-    if dist_on:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    # HIP events on the launch stream around every launch of the three residual-convolution kernels inside the timed region
-    # (recorded inside the library, pcgan_timer_*: whichever host path -- per-op call or composite -- issues the launch)
-    ops.timer_enable(36 * args.steps + 8)
-    if dist_on:
-        parallel.COMM_TIMER = []
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    t_issued = time.perf_counter() - t0     # host side done issuing (the GPU may still be running): launch-bound if ~ dt
-    torch.cuda.synchronize()
-    if dist_on:
-        torch.distributed.barrier()
-    dt = dt_rank = time.perf_counter() - t0
-    per_rank = None
-    if dist_on:
-        t = torch.tensor([dt], device=device, dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt = float(t.item())
-        # per-rank view (diagnostics of the first multi-GPU runs): own wall time and the time inside the gradient all-reduces
-        # (collective + waiting for the slowest rank), HIP events on the launch stream
-        comm, parallel.COMM_TIMER = parallel.COMM_TIMER, None
-        comm_ms = sum(a.elapsed_time(b) for a, b in comm) / args.steps
-        mine = {'rank': rank, 'ms_per_step': round(dt_rank / args.steps * 1e3, 3), 'allreduce_ms_per_step': round(comm_ms, 3),
-                'allreduces_per_step': round(len(comm) / args.steps, 2), 'host_issue_ms_per_step': round(t_issued / args.steps * 1e3, 3)}
-        mine.update(parallel.rank_identity(device))       # device uuid / PCI bus / RCCL version: the record proves N distinct GPUs
-        # replicas must be bit-identical after the timed steps (same start, same averaged gradients, same Adam arithmetic): compared
-        # once, outside the timed region; a divergence puts every rank's hash on stderr and `false` in the line
-        model.sync_parameter_updates()
-        try:
-            mine['replicas_bit_equal'] = bool(parallel.ddp_check(model.optimizer_G, 'bench_G', every=1, exit_on_divergence=False)
-                                              and parallel.ddp_check(model.optimizer_D, 'bench_D', every=1, exit_on_divergence=False))
-        except parallel.ReplicaDivergenceError:       # (raised on every rank alike; each has printed its hash) the line still goes out, flagged
-            mine['replicas_bit_equal'] = False
-        per_rank = [None] * world
-        torch.distributed.all_gather_object(per_rank, mine)
-        uuids = {(r['host'], r.get('device_uuid'), r.get('pci_bus_id')) for r in per_rank}
-        if torch.distributed.get_backend() == 'nccl':
-            assert len(uuids) == world, 'bench.py --gpus %d: ranks share a GPU (%d distinct devices): %r' % (world, len(uuids), sorted(uuids))
-    losses = model.get_current_losses()
-    assert all(v == v and abs(v) < 1e6 for v in losses.values()), 'non-finite loss: %r' % losses
-    _progress('timed region done: %.2f ms/step' % (dt / args.steps * 1e3))
-
     timed = {k: ops.timer_read(k) for k in ('res_fwd', 'res_dgrad', 'res_wgrad', 'res_wgrad_main')}
     # the same kernels running ALONE: three more steps with the parameter-gradient and branch streams off (in the step the data
     # gradient on the main stream and the weight gradient on the side stream share the GPU, so each in-region duration above holds
@@ -336,9 +273,7 @@ def main():
     idle_issue.sort()
     host_ms = idle_issue[len(idle_issue) // 2] * 1e3
     if rank != 0:
-        return
-    ms_per_step = dt / args.steps * 1e3
-    value = PER_GPU_BATCH * world * args.steps / dt
+        return None
     assert all(len(timed[k]) > 0 for k in ('res_fwd', 'res_dgrad', 'res_wgrad')), 'the residual convolutions were not launched inside the timed region'
     kern = {k: {'ms_per_launch': sum(v) / len(v), 'launches_timed': len(v)} for k, v in timed.items() if v}
     conv_flop = RES_CONV_FLOP
@@ -431,20 +366,6 @@ def main():
                 'kernels': per_kernel}
     step_tflops = GFLOP_PER_IMG_FULL * 1e9 * value / world / 1e12        # algorithmic FLOP of the whole step per GPU and second
     out = {
-        'metric': 'images/sec (G+D step) 128x128 bs32 per GPU', 'value': round(value, 3), 'unit': 'images/sec',
-        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3),
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16' if bf16 else 'f32',
-        # what the matrix pipe actually multiplies (dtype above = the storage / interface type of every tensor)
-        'arithmetic': ('bf16 x bf16 products, fp32 accumulate' if bf16 else
-                       '2 scaled fp16 pieces per fp32 operand x 3 piece products (hi*hi, hi*lo, lo*hi), fp32 accumulate: ~22-bit significand '
-                       '(error vs float64 at the fp32 MFMA level, tests/test_gpu_bf16x6.py)' if hsplit else
-                       '3 bf16 pieces per fp32 operand x 6 piece products, fp32 accumulate' if split else 'fp32 MFMA'),
-        'data': 'synthetic', 'input': ('%d distinct batches RESIDENT in HBM (A/B run, not the headline form)' % N_BATCHES) if args.resident_inputs else
-        '%d distinct pinned-host batches, uploaded inside the timed region (set_input)' % N_BATCHES,
-        'config': {'workload': 'wsgan_emb UTKFace-shaped 128x128 bs32/GPU %s: 9-block ResnetGenerator + 3-layer '
-                               'PatchGAN + ResNet-18 Elo encoder@224 + AlexNet IP@224, full optimize_parameters()' % (
-                                   'bf16 activations (fp32 master weights, accumulation, statistics, losses, Adam)' if bf16 else 'fp32'),
-                   'global_batch': PER_GPU_BATCH * world, 'parallelism': 'dp%d' % world},
         # host work: median time to issue one step from an idle GPU (5 steps after the region); in the region the launch queue's
         # back-pressure makes the issue time follow the GPU time (second number)
         'host_issue_ms_per_step': round(host_ms, 3),
@@ -456,10 +377,7 @@ def main():
         'step_frac_of_route_bound': round(step_tflops / peak, 4) if peak else None,
         'step_flop_over_fp32_mfma_peak_not_a_roofline_fraction': round(step_tflops / FP32_MFMA_PEAK_TFLOPS, 4),
         'roofline': roof,
-        'losses': {k: round(v, 5) for k, v in losses.items()},
     }
-    if per_rank is not None:
-        out['per_rank'] = per_rank
     if world == 1 and not args.no_experiment and ops.BF16X6 and not bf16:
         # NOT the headline: the same K steps once more with the 108 residual-convolution launches on the two other routes -- the
         # exact three-piece bf16 split (PCGAN_SPLIT=bf16, the default before the fp16 route) and the fp32 MFMA implicit GEMM
@@ -490,6 +408,149 @@ def main():
     if world == 1 and not args.no_cpu_baseline:
         _progress('cpu baseline')
         out['cpu_baseline'] = cpu_baseline()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gpus', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps')
+    ap.add_argument('--warmup', type=int, default=5, help='untimed steps before them')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: residual-convolution roofline and kernel timings, host issue time, '
+                         'the other convolution routes, per-rank diagnostics, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed (fake_B, rec_A, the losses, a seeded sample of the G / D / E state) '
+                         'as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'],
+                    help='activation storage type; the headline (BASELINE configs[1]) is fp32, bf16 is BASELINE configs[2] per GPU')
+    ap.add_argument('--resident-inputs', action='store_true',
+                    help='A/B only: keep the synthetic batches in HBM (no upload inside the timed region); the headline uploads them')
+    ap.add_argument('--no-experiment', action='store_true',
+                    help='with --full: skip the extra (not headline) run with the residual convolutions routed back to the fp32 MFMA kernels')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+
+    # stdout carries the ONE JSON line and nothing else: native libraries write to file descriptor 1 behind Python's back (RCCL prints
+    # a five-line version banner on rank 0's stdout when its communicator comes up -- seen on the first RCCL run, round 4), so the
+    # descriptor itself points at stderr until the line is printed
+    sys.stdout.flush()
+    json_fd = os.dup(1)
+    os.dup2(2, 1)
+
+    from pcgan_amd.hip import parallel
+    world, rank, local = parallel.init_process_group()
+    assert world == args.gpus, 'launch with torchrun --nproc-per-node %d (WORLD_SIZE=%d)' % (args.gpus, world)
+    assert torch.cuda.is_available(), 'bench.py needs an MI355X (no CPU fallback)'
+    dev_index = local % torch.cuda.device_count()   # (one GPU per rank on a real node; a 1-GPU box can only rehearse)
+    torch.cuda.set_device(dev_index)
+    device = torch.device('cuda', dev_index)
+
+    tmpdir = tempfile.mkdtemp(prefix='pcgan_bench_')
+    with contextlib.redirect_stdout(sys.stderr):      # the reference's 'initialize network with ...' notices: stdout carries the JSON line only
+        model, opt = build_model(dev_index, PER_GPU_BATCH, SIZE, tmpdir, dtype=args.dtype)
+    # N_BATCHES distinct batches in PINNED host memory: set_input uploads them INSIDE the timed region (BaseModel.to_act: async copy on
+    # the upload stream, 2 x 6.3 MB + the labels per step -- SURVEY 8(a2) is part of the step; round 3 parked two batches in HBM)
+    batches = [synthetic_batch(PER_GPU_BATCH, SIZE, rank, it) for it in range(N_BATCHES)]
+    batches = [{k: (v.pin_memory() if isinstance(v, torch.Tensor) else v) for k, v in b.items()} for b in batches]
+    if args.resident_inputs:      # A/B only (round 3's form): batches parked in HBM before the region, declared ready by their producer
+        from pcgan_amd.hip import ops as _ops
+        batches = [{k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in b.items()} for b in batches]
+        torch.cuda.synchronize()
+        for b in batches:
+            _ops.mark_ready(b['A'])
+            _ops.mark_ready(b['B'])
+
+    def step(i):
+        model.set_input(batches[i % N_BATCHES])
+        model.optimize_parameters()
+
+    from pcgan_amd.hip import ops
+    _progress('model built, warm-up')
+    for i in range(args.warmup):
+        step(i)
+    dist_on = parallel.is_distributed()     # more than one rank, or the one-rank RCCL rehearsal (PCGAN_FORCE_COLLECTIVES=1)
+    _progress('timed region')
+    if dist_on:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    if args.full:
+        # HIP events on the launch stream around every launch of the three residual-convolution kernels inside the timed region
+        # (recorded inside the library, pcgan_timer_*: whichever host path -- per-op call or composite -- issues the launch)
+        ops.timer_enable(36 * args.steps + 8)
+        if dist_on:
+            parallel.COMM_TIMER = []
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        step(i)
+    t_issued = time.perf_counter() - t0     # host side done issuing (the GPU may still be running): launch-bound if ~ dt
+    torch.cuda.synchronize()
+    if dist_on:
+        torch.distributed.barrier()
+    dt = dt_rank = time.perf_counter() - t0
+    per_rank = None
+    if dist_on:
+        t = torch.tensor([dt], device=device, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        dt = float(t.item())
+    if dist_on and args.full:
+        # per-rank view (diagnostics of the first multi-GPU runs): own wall time and the time inside the gradient all-reduces
+        # (collective + waiting for the slowest rank), HIP events on the launch stream
+        comm, parallel.COMM_TIMER = parallel.COMM_TIMER, None
+        comm_ms = sum(a.elapsed_time(b) for a, b in comm) / args.steps
+        mine = {'rank': rank, 'ms_per_step': round(dt_rank / args.steps * 1e3, 3), 'allreduce_ms_per_step': round(comm_ms, 3),
+                'allreduces_per_step': round(len(comm) / args.steps, 2), 'host_issue_ms_per_step': round(t_issued / args.steps * 1e3, 3)}
+        mine.update(parallel.rank_identity(device))       # device uuid / PCI bus / RCCL version: the record proves N distinct GPUs
+        # replicas must be bit-identical after the timed steps (same start, same averaged gradients, same Adam arithmetic): compared
+        # once, outside the timed region; a divergence puts every rank's hash on stderr and `false` in the line
+        model.sync_parameter_updates()
+        try:
+            mine['replicas_bit_equal'] = bool(parallel.ddp_check(model.optimizer_G, 'bench_G', every=1, exit_on_divergence=False)
+                                              and parallel.ddp_check(model.optimizer_D, 'bench_D', every=1, exit_on_divergence=False))
+        except parallel.ReplicaDivergenceError:       # (raised on every rank alike; each has printed its hash) the line still goes out, flagged
+            mine['replicas_bit_equal'] = False
+        per_rank = [None] * world
+        torch.distributed.all_gather_object(per_rank, mine)
+        uuids = {(r['host'], r.get('device_uuid'), r.get('pci_bus_id')) for r in per_rank}
+        if torch.distributed.get_backend() == 'nccl':
+            assert len(uuids) == world, 'bench.py --gpus %d: ranks share a GPU (%d distinct devices): %r' % (world, len(uuids), sorted(uuids))
+    losses = model.get_current_losses()
+    assert all(v == v and abs(v) < 1e6 for v in losses.values()), 'non-finite loss: %r' % losses
+    _progress('timed region done: %.2f ms/step' % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, losses, args.dump_outputs)      # before any --full step moves the model on
+
+    ms_per_step = dt / args.steps * 1e3
+    value = PER_GPU_BATCH * world * args.steps / dt
+    full = full_measurements(args, model, step, world, rank, value, t_issued) if args.full else None
+    if rank != 0:
+        return
+    split = ops.BF16X6
+    hsplit = split and ops.HSPLIT
+    bf16 = args.dtype == 'bf16'
+    out = {
+        'metric': 'images/sec (G+D step) 128x128 bs32 per GPU', 'value': round(value, 3), 'unit': 'images/sec',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16' if bf16 else 'f32',
+        # what the matrix pipe actually multiplies (dtype above = the storage / interface type of every tensor)
+        'arithmetic': ('bf16 x bf16 products, fp32 accumulate' if bf16 else
+                       '2 scaled fp16 pieces per fp32 operand x 3 piece products (hi*hi, hi*lo, lo*hi), fp32 accumulate: ~22-bit significand '
+                       '(error vs float64 at the fp32 MFMA level, tests/test_gpu_bf16x6.py)' if hsplit else
+                       '3 bf16 pieces per fp32 operand x 6 piece products, fp32 accumulate' if split else 'fp32 MFMA'),
+        'data': 'synthetic', 'input': ('%d distinct batches RESIDENT in HBM (A/B run, not the headline form)' % N_BATCHES) if args.resident_inputs else
+        '%d distinct pinned-host batches, uploaded inside the timed region (set_input)' % N_BATCHES,
+        'config': {'workload': 'wsgan_emb UTKFace-shaped 128x128 bs32/GPU %s: 9-block ResnetGenerator + 3-layer '
+                               'PatchGAN + ResNet-18 Elo encoder@224 + AlexNet IP@224, full optimize_parameters()' % (
+                                   'bf16 activations (fp32 master weights, accumulation, statistics, losses, Adam)' if bf16 else 'fp32'),
+                   'global_batch': PER_GPU_BATCH * world, 'parallelism': 'dp%d' % world},
+        'losses': {k: round(v, 5) for k, v in losses.items()},
+    }
+    if full is not None:
+        out.update(full)
+    if per_rank is not None:
+        out['per_rank'] = per_rank
     _progress('done')
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + '\n').encode())

@@ -6,7 +6,7 @@ OUT=$1; VAR=$2; A=$3; B=$4; R=${5:-3}
 mkdir -p $OUT
 for i in $(seq 1 $R); do
   for V in $A $B; do
-    env $VAR=$V python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-experiment > $OUT/ab_${VAR}_${V}_$i.json 2> $OUT/ab_${VAR}_${V}_$i.err || { tail -5 $OUT/ab_${VAR}_${V}_$i.err; exit 1; }
+    env $VAR=$V python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-experiment > $OUT/ab_${VAR}_${V}_$i.json 2> $OUT/ab_${VAR}_${V}_$i.err || { tail -5 $OUT/ab_${VAR}_${V}_$i.err; exit 1; }
     python - <<PY
 import json
 d = json.load(open('$OUT/ab_${VAR}_${V}_$i.json'))

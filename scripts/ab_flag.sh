@@ -5,7 +5,7 @@ mkdir -p $OUT
 for i in $(seq 1 $R); do
   for V in A B; do
     F=$A; [ $V = B ] && F=$B
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-experiment $F > $OUT/ab_${TAG}_${V}_$i.json 2> $OUT/ab_${TAG}_${V}_$i.err || { tail -5 $OUT/ab_${TAG}_${V}_$i.err; exit 1; }
+    python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-experiment $F > $OUT/ab_${TAG}_${V}_$i.json 2> $OUT/ab_${TAG}_${V}_$i.err || { tail -5 $OUT/ab_${TAG}_${V}_$i.err; exit 1; }
     python - <<PY
 import json
 d = json.load(open('$OUT/ab_${TAG}_${V}_$i.json'))

@@ -7,11 +7,11 @@ mkdir -p gpurun_out
 OUT=gpurun_out/ab_rccl1.txt
 : > $OUT
 run() {   # label, env...
-    local label=$1; shift
-    env "$@" python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-experiment > gpurun_out/_ab.json 2> gpurun_out/_ab.err || { tail -5 gpurun_out/_ab.err; exit 1; }
-    python - "$label" <<'PY' >> gpurun_out/ab_rccl1.txt
+    local label=$1 run=${OUT%.txt}_run; shift
+    env "$@" python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-experiment > $run.json 2> $run.err || { tail -5 $run.err; exit 1; }
+    python - "$label" "$run.json" <<'PY' >> $OUT
 import json, sys
-lines = [l for l in open('gpurun_out/_ab.json') if l.strip()]
+lines = [l for l in open(sys.argv[2]) if l.strip()]
 assert len(lines) == 1, 'stdout must carry the one JSON line: %r' % lines
 d = json.loads(lines[0])
 pr = (d.get('per_rank') or [{}])[0]

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-experiment"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-experiment"
 show() { tail -1 $1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$2', d['ms_per_step'], 'host', d['host_issue_ms_per_step'], 'kernel', d['roofline']['ms_per_launch'])"; }
 $B > gpurun_out/ab_default.txt 2>&1; show gpurun_out/ab_default.txt default
 PCGAN_SPLIT=bf16 $B > gpurun_out/ab_bf16.txt 2>&1; show gpurun_out/ab_bf16.txt split=bf16

@@ -1,17 +1,19 @@
-"""CPU: the bench.py contract -- flags, and the shape of the JSON line (checked on the latest line committed under
-profiles/, which bench.py printed on an MI355X)."""
+"""The bench.py contract.  CPU: flags, and the shape of the JSON line (checked on the latest line committed under profiles/, which
+bench.py printed on an MI355X).  GPU: a plain run's line and its --dump-outputs files."""
 import glob
 import json
 import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_flags_and_defaults():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, cwd=ROOT).stdout
-    for flag in ('--gpus', '--steps', '--warmup'):
+    for flag in ('--gpus', '--steps', '--warmup', '--full', '--dump-outputs'):
         assert flag in out
     import bench
     assert bench.PER_GPU_BATCH == 32 and bench.SIZE == 128 and bench.GFLOP_PER_IMG_FULL == 183.95
@@ -62,3 +64,31 @@ def test_cpu_budget_is_cgroup_aware():
     import bench
     n, why = bench.host_cpu_budget()
     assert 1 <= n <= (os.cpu_count() or 1) and 'affinity' in why
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_outputs(dev, tmp_path):
+    """a plain run prints the headline fields only, over exactly --steps timed steps, and --dump-outputs writes the last step's
+    outputs (float32 / float64, under 64 MB); the same arguments give the same outputs (seeded inputs and weights)"""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ('out%d' % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--dump-outputs', str(d)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line['steps'] == 2 and line['warmup'] == 1 and line['unit'] == 'images/sec' and line['higher_is_better'] is True
+        assert line['dtype'] == 'f32' and line['ms_per_step'] > 0 and abs(line['value'] - 32 / line['ms_per_step'] * 1e3) < 0.01 * line['value']
+        assert not {'roofline', 'cpu_baseline', 'route_fp32_mfma', 'host_issue_ms_per_step'} & set(line), sorted(line)
+        files = sorted(os.listdir(d))
+        assert {'fake_B.npy', 'rec_A.npy', 'loss_G_GAN.npy', 'loss_D_fake.npy', 'G_state_sample.npy', 'D_state_sample.npy'} <= set(files), files
+        assert sum(os.path.getsize(d / f) for f in files) < 64 << 20
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert arrays['fake_B.npy'].shape == (32, 3, 128, 128)
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f
