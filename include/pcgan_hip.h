@@ -270,6 +270,23 @@ int pcgan_image_transform_band(const pcgan_image_desc* d, const int32_t* bv_host
 int pcgan_image_transform(const pcgan_image_desc* d, const uint8_t* src, const int32_t* kh, const int32_t* bh,
                           const int32_t* kv, const int32_t* bv, const int32_t* aug, float* out, int n, int band,
                           int max_rows, pcgan_stream_t s);
+/* The affine modes (get_transform 'resize_affine_crop' / 'resize_affine_center', data/base_dataset.py:41-52:
+ * Resize([loadSize, loadSize], BICUBIC) -> RandomAffine(degrees, scale, BICUBIC, fillcolor=127) ->
+ * RandomCrop / CenterCrop(fineSize) -> RandomHorizontalFlip -> ToTensor -> Normalize) in two launches:
+ * pcgan_image_resize_u8: the resize alone, src[n][H][W][3] -> out[n][RH][RW][3] uint8, same tables and
+ * band as pcgan_image_transform with the window the whole image (FH = RH, FW = RW; the bytes the PIL
+ * path's Image.resize returns).
+ * pcgan_image_affine: Pillow's Image.transform(AFFINE, BICUBIC, fillcolor=127) of the resized images
+ * (d->RH x d->RW, mat[n][6] doubles: the inverse matrix, output pixel centre -> input position) read at
+ * the crop window (aug[n][4] = crop x0, crop y0, flip, dst index; 0 <= x0 <= RW - FW, 0 <= y0 <= RH - FH
+ * checked by the caller), flipped, normalised into out[dst][out_channels][FH][FW] fp32 (1 channel: the
+ * gray mix).  Double arithmetic in Pillow's order, bit-exact with the PIL path; the fill is (127, 0, 0),
+ * the reference's integer fill colour on an RGB image.  d->H, W, ksize_* are not read. */
+int pcgan_image_resize_u8(const pcgan_image_desc* d, const uint8_t* src, const int32_t* kh, const int32_t* bh,
+                          const int32_t* kv, const int32_t* bv, uint8_t* out, int n, int band, int max_rows,
+                          pcgan_stream_t s);
+int pcgan_image_affine(const pcgan_image_desc* d, const uint8_t* resized, const double* mat, const int32_t* aug,
+                       float* out, int n, pcgan_stream_t s);
 
 /* ---- convolution on the bf16 matrix pipe (v_mfma_f32_32x32x16_bf16, fp32 accumulators) -----------
  * Same call sites as pcgan_conv2d_fwd_packed for stride-1 convolutions with C % 16 == 0, K >= 32, at most 25 taps

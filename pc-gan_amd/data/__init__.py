@@ -34,7 +34,8 @@ def create_dataset(opt):
 
 
 def _collate_keep_raw(samples):
-    """default collate, except that decoded images ('*_raw', possibly of different sizes) stay a list"""
+    """default collate, except that decoded images ('*_raw', possibly of different sizes) stay a list; their draws ('*_aug',
+    affine matrix included) stack into one tensor"""
     raw = {k: [s[k] for s in samples] for k in samples[0] if k.endswith('_raw')}
     rest = torch.utils.data.default_collate([{k: v for k, v in s.items() if not k.endswith('_raw')} for s in samples])
     rest.update(raw)
@@ -96,8 +97,8 @@ class CustomDatasetDataLoader(object):
         self.dataset = create_dataset(opt)
         self.gpu_transform = None
         if getattr(opt, 'gpu_transform', False) and opt.dataroot != 'synthetic':
-            from .gpu_transform import GpuTransform
-            self.gpu_transform = GpuTransform(opt, 'cuda:%d' % opt.gpu_ids[0] if opt.gpu_ids else 'cpu')
+            from .gpu_transform import make_gpu_transform
+            self.gpu_transform = make_gpu_transform(opt, 'cuda:%d' % opt.gpu_ids[0] if opt.gpu_ids else 'cpu')
         collate = _collate_keep_raw if self.gpu_transform else None
         self.sampler = None
         # pinned batches: set_input's upload (BaseModel.to_act) is then an asynchronous copy on the upload stream whose event the
@@ -130,7 +131,8 @@ class CustomDatasetDataLoader(object):
 
     def _finish_on_gpu(self, batch):
         """'<key>_raw' + '<key>_aug' -> '<key>': one image-pipeline launch per image set (A with input_nc channels, B
-        with output_nc, the gray mix of the pair dataset included)"""
+        with output_nc, the gray mix of the pair dataset included).  '<key>_aug' is the collated draws of decode_raw: int32
+        (x0, y0, flip), or for the affine modes float64 (x0, y0, flip, m0 .. m5) -- the inverse matrix rides along"""
         for raw_key in [k for k in batch if k.endswith('_raw')]:
             key = raw_key[:-4]
             channels = self.opt.input_nc if key.endswith('A') else self.opt.output_nc

@@ -81,16 +81,23 @@ def _inverse_affine_matrix(center, angle, translate, scale, shear):
     return matrix
 
 
-def random_affine(img, degrees, scale_range):
-    """transforms.RandomAffine(degrees, scale=scale_range, resample=BICUBIC, fillcolor=127) of the reference's two affine modes
-    (data/base_dataset.py:41-52): angle ~ U(-degrees, degrees), scale ~ U(scale_range), no translation / shear, about the image
-    centre.  Draws from `random` (angle first, then scale).  torchvision is absent here: this restates its published algorithm and
-    is NOT pinned by a golden vector."""
-    from PIL import Image
+def draw_affine(w, h, degrees, scale_range):
+    """the RandomAffine draw of the reference's two affine modes for a w x h image: angle ~ U(-degrees, degrees), then scale ~
+    U(scale_range), from `random`; returns the inverse matrix (six doubles) Image.transform takes, rotation / scale about the image
+    centre, no translation / shear.  Both the PIL path (random_affine) and the GPU path (decode_raw) take their matrix from here."""
     angle = random.uniform(-degrees, degrees)
     scale = random.uniform(scale_range[0], scale_range[1])
+    return _inverse_affine_matrix((w * 0.5 + 0.5, h * 0.5 + 0.5), angle, (0, 0), scale, 0.0)
+
+
+def random_affine(img, degrees, scale_range):
+    """transforms.RandomAffine(degrees, scale=scale_range, resample=BICUBIC, fillcolor=127) of the reference's two affine modes
+    (data/base_dataset.py:41-52): the draw of draw_affine, then Pillow's warp.  torchvision is absent here: the draw restates its
+    published algorithm and is NOT pinned by a golden vector; the warp is Pillow's own, restated bit-exactly
+    by tests/affine_ref.py and the GPU kernel."""
+    from PIL import Image
     w, h = img.size
-    matrix = _inverse_affine_matrix((w * 0.5 + 0.5, h * 0.5 + 0.5), angle, (0, 0), scale, 0.0)
+    matrix = draw_affine(w, h, degrees, scale_range)
     return img.transform((w, h), Image.AFFINE, matrix, Image.BICUBIC, fillcolor=127)
 
 
@@ -127,16 +134,27 @@ def get_transform(opt):
     return tf
 
 
+AFFINE_MODES = ('resize_affine_crop', 'resize_affine_center')
+
+
 def decode_raw(img, opt):
     """--gpu_transform: what a worker hands to the loader instead of the transformed tensor -- the decoded image as a
-    uint8 (H, W, 3) tensor and the (x0, y0, flip) draws of get_transform, taken from `random` in the same order."""
+    uint8 (H, W, 3) tensor and the draws of get_transform, taken from `random` in the same order.  The draws are int32
+    (x0, y0, flip), or for the affine modes float64 (x0, y0, flip, m0 .. m5): the crop offsets and flip after the six
+    doubles of the inverse affine matrix (drawn first: angle, scale), on the resized size as the PIL path does."""
     from .gpu_transform import draw_augmentation
-    if opt.transforms in ('resize_affine_crop', 'resize_affine_center'):
-        raise NotImplementedError('pcgan_amd: --gpu_transform does not cover the affine modes (--transforms %s); the loader\'s PIL '
-                                  'path (no --gpu_transform) does' % opt.transforms)
     w, h = img.size
-    resized, fs, _ = resize_plan(opt, w, h)
+    resized, fs, centre = resize_plan(opt, w, h)
     if resized is not None:
         w, h = resized
+    raw = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy())
+    if opt.transforms in AFFINE_MODES:
+        matrix = draw_affine(w, h, opt.affineDegrees, tuple(opt.affineScale))
+        if centre:
+            x0, y0 = int(round((w - fs) / 2.0)), int(round((h - fs) / 2.0))
+            flip = 1 if (opt.isTrain and not opt.no_flip and random.random() < 0.5) else 0
+        else:
+            x0, y0, flip = draw_augmentation(w, h, fs, opt.isTrain and not opt.no_flip)
+        return raw, torch.tensor([x0, y0, flip] + list(matrix), dtype=torch.float64)
     aug = draw_augmentation(w, h, fs, opt.isTrain and not opt.no_flip)
-    return torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()), torch.tensor(aug, dtype=torch.int32)
+    return raw, torch.tensor(aug, dtype=torch.int32)

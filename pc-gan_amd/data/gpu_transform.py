@@ -8,6 +8,11 @@ fixed point.  `resample_table` rebuilds Pillow's coefficient tables (libImaging/
 precompute_coeffs, normalize_coeffs_8bpc) in the same double arithmetic, the kernel applies them in integers, so the
 batch equals the PIL path bit for bit (tests/test_gpu_transform.py holds it to `Image.resize` itself).
 
+The two affine modes (`Resize -> RandomAffine(BICUBIC, fillcolor=127) -> RandomCrop / CenterCrop -> flip`) go through
+`GpuAffineTransform`: the same resize into whole uint8 images (`pcgan_image_resize_u8`), then Pillow's bicubic affine warp
+read at the crop window (`pcgan_image_affine`, double arithmetic in Pillow's order: bit-exact as well, tests/affine_ref.py).
+`make_gpu_transform` picks the class from `--transforms`.
+
 JPEG/PNG decoding stays in the DataLoader workers; what moves to the GPU is the per-pixel work (4.7 ms per image and
 core with PIL at 200x200 -> 143x143 -> 128x128 on the MI355X box's host, scripts/bench_transform.py).
 """
@@ -99,8 +104,9 @@ class GpuTransform(object):
 
     def __init__(self, opt, device):
         if opt.transforms not in ('resize_and_crop', 'crop', 'scale_width', 'scale_width_and_crop', 'none'):
-            raise NotImplementedError('pcgan_amd: the GPU image pipeline does not cover --transforms %s (the affine modes run on the '
-                                      'loader\'s PIL path: drop --gpu_transform)' % opt.transforms)
+            raise NotImplementedError('pcgan_amd: GpuTransform does not cover --transforms %s: the affine modes (resize_affine_crop, '
+                                      'resize_affine_center) run through GpuAffineTransform (make_gpu_transform picks the class)'
+                                      % opt.transforms)
         self.opt = opt
         self.fine = opt.fineSize
         self.device = torch.device(device)
@@ -169,3 +175,75 @@ class GpuTransform(object):
         from ..hip import ops
         ops.mark_ready(out)      # producer's event: the step's ahead-of-time passes over this batch wait for THIS, not for the main stream
         return out
+
+
+class GpuAffineTransform(GpuTransform):
+    """callable: list of uint8 (H, W, 3) tensors + per-image draws (x0, y0, flip, m0 .. m5) -> float (n, C, fine, fine) on `device`,
+    for --transforms resize_affine_crop / resize_affine_center (base_dataset.decode_raw draws them; m = the inverse affine matrix on
+    the resized image).  Per source size: one resize launch into a uint8 scratch of whole resized images, one warp launch."""
+
+    def __init__(self, opt, device):
+        from .base_dataset import AFFINE_MODES
+        if opt.transforms not in AFFINE_MODES:
+            raise NotImplementedError('pcgan_amd: GpuAffineTransform covers the affine modes %s only (got --transforms %s; '
+                                      'GpuTransform takes the others)' % (AFFINE_MODES, opt.transforms))
+        self.opt = opt
+        self.fine = opt.fineSize
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('pcgan_amd: the GPU image pipeline needs a GPU device (got %s); there is no fallback' % device)
+        self._geo = {}
+        self._resize = {}       # (H, W) -> _Geometry of the whole-image uint8 resize
+        self._stage = {}
+
+    def resize_geometry(self, H, W):
+        key = (H, W)
+        if key not in self._resize:
+            g = self.geometry(H, W, 3)
+            self._resize[key] = _Geometry(H, W, g.RH, g.RW, g.RH, g.RW, 3, self.device)
+        return self._resize[key]
+
+    def __call__(self, images, draws, out_channels=3):
+        n = len(images)
+        draws = torch.as_tensor(draws, dtype=torch.float64).reshape(n, 9)
+        groups = {}
+        for i, im in enumerate(images):
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                raise ValueError('GpuAffineTransform: image %d is not a uint8 (H, W, 3) tensor' % i)
+            groups.setdefault((int(im.shape[0]), int(im.shape[1])), []).append(i)
+        out = torch.empty((n, out_channels, self.fine, self.fine), dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        h = _L.load()
+        for (H, W), idx in groups.items():
+            g, r = self.geometry(H, W, out_channels), self.resize_geometry(H, W)
+            d = draws[idx]
+            a = torch.empty((len(idx), 4), dtype=torch.int32)
+            a[:, :3] = d[:, :3].to(torch.int32)
+            a[:, 3] = torch.as_tensor(idx, dtype=torch.int32)
+            # the kernels trust the offsets: check them where they are still host data
+            if not torch.equal(a[:, :3].to(torch.float64), d[:, :3]) or int(a[:, 2].min()) < 0 or int(a[:, 2].max()) > 1:
+                raise ValueError('GpuAffineTransform: crop offsets / flip must be integers (flip 0 or 1)')
+            if int(a[:, 0].min()) < 0 or int(a[:, 0].max()) > g.RW - g.FW or int(a[:, 1].min()) < 0 \
+                    or int(a[:, 1].max()) > g.RH - g.FH:
+                raise ValueError('GpuAffineTransform: crop offset outside the warped image')
+            src = self._upload([images[i] for i in idx], H, W)
+            resized = torch.empty((len(idx), g.RH, g.RW, 3), dtype=torch.uint8, device=self.device)
+            _L.check(h.pcgan_image_resize_u8(
+                ctypes.byref(r.desc), src.data_ptr(), r.kh.data_ptr(), r.bh.data_ptr(), r.kv.data_ptr(), r.bv.data_ptr(),
+                resized.data_ptr(), len(idx), r.band, r.rows, stream), 'image_resize_u8')
+            a_dev = a.to(self.device, non_blocking=True)
+            m_dev = d[:, 3:].contiguous().to(self.device, non_blocking=True)
+            _L.check(h.pcgan_image_affine(ctypes.byref(g.desc), resized.data_ptr(), m_dev.data_ptr(), a_dev.data_ptr(), out.data_ptr(),
+                                          len(idx), stream), 'image_affine')
+            cur = torch.cuda.current_stream(self.device)
+            a_dev.record_stream(cur)
+            m_dev.record_stream(cur)
+        from ..hip import ops
+        ops.mark_ready(out)      # producer's event (see GpuTransform.__call__)
+        return out
+
+
+def make_gpu_transform(opt, device):
+    """the GPU image pipeline for opt.transforms: GpuAffineTransform for the affine modes, GpuTransform for the others"""
+    from .base_dataset import AFFINE_MODES
+    return (GpuAffineTransform if opt.transforms in AFFINE_MODES else GpuTransform)(opt, device)

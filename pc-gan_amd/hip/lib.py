@@ -142,6 +142,8 @@ SIGNATURES = {
     'pcgan_conv2d_bwd_weight_direct': (_i, [_dp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     'pcgan_image_transform_band': (_i, [_ip, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     'pcgan_image_transform': (_i, [_ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'pcgan_image_resize_u8': (_i, [_ip, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'pcgan_image_affine': (_i, [_ip, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 _lib = None

@@ -9,8 +9,10 @@ Adam; writes `init_net.pth`, `latest_net.pth`, `<epoch>_net.pth` and `loss.txt` 
 Same flag names and defaults as the reference for everything implemented: the deterministic recipe, MC dropout (`--bayesian true
 --bnn_dropout p --T_train T`) and the noisy-rating variants (`--noisy true` with `--rsample`, `--lb_or_mc`, `--M`, a second Adam on
 the log-variance head with `--lr_sigma` and its epoch schedule); no `fc_dim`, no `use_cxn`, no `--finetune_fc_only`; image
-augmentation is resize + random crop + flip (torchvision's affine /
-colour jitter are not available here); `--dataroot synthetic` trains on seeded synthetic pairs whose label is decided
+augmentation is every `--transforms` mode of the loader, the reference's `resize_affine_crop` (resize -> RandomAffine(
+`--affineDegrees`, `--affineScale`, BICUBIC, fill 127) -> random crop -> flip) included -- the default stays
+`resize_and_crop`; `--gpu_transform` moves the per-pixel work of every mode from the DataLoader workers (PIL) to the GPU
+(bit-exact; workers only decode and draw); `--dataroot synthetic` trains on seeded synthetic pairs whose label is decided
 by a hidden per-image score, so the loss must fall.
 
     python siamese.py --dataroot synthetic --name elo --batch_size 32 --num_epochs 2 --pretrained_model_path ''
@@ -23,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from pcgan_amd.data.base_dataset import get_transform
+from pcgan_amd.data.base_dataset import decode_raw, get_transform
 from pcgan_amd.hip import parallel
 from pcgan_amd.hip.optim import FusedAdam
 from pcgan_amd.models import networks
@@ -61,6 +63,11 @@ def build_parser():
     add('--print_freq', type=int, default=10)
     add('--display_id', type=int, default=-1)
     add('--transforms', type=str, default='resize_and_crop')
+    add('--affineScale', nargs='+', type=float, default=[0.95, 1.05], help='scale tuple in transforms.RandomAffine')
+    add('--affineDegrees', type=float, default=5, help='range of degrees in transforms.RandomAffine')
+    add('--gpu_transform', action='store_true',
+        help='(pcgan_amd) resize / affine / crop / flip / normalise on the GPU, bit-exact with the PIL path; the DataLoader '
+             'workers only decode images and draw the augmentation')
     add('--no_flip', action='store_true')
     add('--continue_train', action='store_true')
     add('--which_epoch', type=str, default='latest')
@@ -98,6 +105,7 @@ class PairDataset(torch.utils.data.Dataset):
         self.n = len(self.lines)
         opt.isTrain = True
         self.transform = get_transform(opt)
+        self.raw = bool(getattr(opt, 'gpu_transform', False))
 
     def __len__(self):
         return self.n
@@ -113,9 +121,46 @@ class PairDataset(torch.utils.data.Dataset):
             return imgs[0], imgs[1], torch.tensor(label)
         from PIL import Image
         a, b, lab = self.lines[i][:3]
+        if self.raw:       # --gpu_transform: decoded bytes + draws (same draws, same order as the PIL path); pair_batch finishes on the GPU
+            A = decode_raw(Image.open(os.path.join(self.root, a)).convert('RGB'), self.opt)
+            B = decode_raw(Image.open(os.path.join(self.root, b)).convert('RGB'), self.opt)
+            return A[0], A[1], B[0], B[1], torch.tensor(int(lab))
         A = self.transform(Image.open(os.path.join(self.root, a)).convert('RGB'))
         B = self.transform(Image.open(os.path.join(self.root, b)).convert('RGB'))
         return A, B, torch.tensor(int(lab))
+
+
+def collate_keep_raw(samples):
+    """--gpu_transform: decoded images (uint8 (H, W, 3), possibly of different sizes) stay lists, everything else collates as usual"""
+    out = []
+    for col in zip(*samples):
+        if torch.is_tensor(col[0]) and col[0].dtype == torch.uint8 and col[0].dim() == 3:
+            out.append(list(col))
+        else:
+            out.append(torch.utils.data.default_collate(col))
+    return out
+
+
+def gpu_pipeline(opt, data, device):
+    """the GPU image pipeline of --gpu_transform for a data set that decodes (None: PIL path, or synthetic data)"""
+    if not getattr(opt, 'gpu_transform', False) or data.synthetic:
+        return None
+    from pcgan_amd.data.gpu_transform import make_gpu_transform
+    return make_gpu_transform(opt, device)
+
+
+def make_loader(opt, data, tf, **kw):
+    return torch.utils.data.DataLoader(data, num_workers=0 if data.synthetic else opt.num_workers,
+                                       collate_fn=collate_keep_raw if tf is not None else None, **kw)
+
+
+def pair_batch(batch, tf, device, rank=0, world=1):
+    """(img0, img1, label) of this rank on `device`: with --gpu_transform only this rank's slice of the global batch is transformed
+    (the rows of the full transform: the draws were taken per image in the workers)"""
+    if tf is None:
+        return tuple(parallel.shard_batch(t, rank, world).to(device) for t in batch)
+    raw0, aug0, raw1, aug1, label = (parallel.shard_batch(t, rank, world) for t in batch)
+    return tf(raw0, aug0), tf(raw1, aug1), label.to(device)
 
 
 def init_like_reference(net):
@@ -226,16 +271,16 @@ def train(opt):
         optimizer_sigma = FusedAdam(net.cnn_logvar.parameters(), lr=opt.lr_sigma)
         scheduler_sigma = torch.optim.lr_scheduler.LambdaLR(optimizer_sigma, lr_lambda=sigma_lr_rule(opt))
     data = PairDataset(opt, opt.dataroot, opt.datafile)
-    loader = torch.utils.data.DataLoader(data, batch_size=opt.batch_size, shuffle=not opt.serial_batches,
-                                         num_workers=0 if data.synthetic else opt.num_workers)
+    tf = gpu_pipeline(opt, data, device)
+    loader = make_loader(opt, data, tf, batch_size=opt.batch_size, shuffle=not opt.serial_batches)
     save_dir = os.path.join(opt.checkpoint_dir, opt.name)
     os.makedirs(save_dir, exist_ok=True)
     save(net, os.path.join(save_dir, 'init_net.pth'))
     history, total = [], 0
     for epoch in range(opt.epoch_count, opt.num_epochs + opt.epoch_count):
         wrong = seen = 0
-        for img0, img1, label in loader:
-            img0, img1, label = (parallel.shard_batch(t, rank, world).to(device) for t in (img0, img1, label))
+        for batch in loader:
+            img0, img1, label = pair_batch(batch, tf, device, rank, world)
             total += 1
             optimizer.zero_grad()
             if optimizer_sigma is not None:
@@ -288,6 +333,7 @@ class SingleImageDataset(torch.utils.data.Dataset):
             self.lines = sorted(os.listdir(root))[:opt.max_dataset_size]
         if not self.synthetic:
             self.transform = get_transform(opt)
+        self.raw = bool(getattr(opt, 'gpu_transform', False))
 
     def __len__(self):
         return len(self.lines)
@@ -299,7 +345,11 @@ class SingleImageDataset(torch.utils.data.Dataset):
             s = self.opt.fineSize
             return torch.rand(3, s, s, generator=g) * 0.5 + level - 0.75, self.lines[i]
         from PIL import Image
-        return self.transform(Image.open(os.path.join(self.root, self.lines[i].split()[0])).convert('RGB')), self.lines[i]
+        img = Image.open(os.path.join(self.root, self.lines[i].split()[0])).convert('RGB')
+        if self.raw:       # --gpu_transform: decoded bytes + draws
+            raw, aug = decode_raw(img, self.opt)
+            return raw, aug, self.lines[i]
+        return self.transform(img), self.lines[i]
 
 
 def get_attr_value(fname):
@@ -346,12 +396,19 @@ def embedding(opt, net=None, which_epoch=None):
         net = build_feature_net(opt, device)
     which_epoch = which_epoch or opt.which_epoch
     data = SingleImageDataset(opt, opt.dataroot, opt.datafile)
-    loader = torch.utils.data.DataLoader(data, shuffle=False, num_workers=0, batch_size=1)
+    tf = gpu_pipeline(opt, data, device)
+    loader = torch.utils.data.DataLoader(data, shuffle=False, num_workers=0, batch_size=1,
+                                         collate_fn=collate_keep_raw if tf is not None else None)
     features, labels, stds, variances = [], [], [], []
     fd = net.feature_dim
     with torch.no_grad():
-        for img0, path0 in loader:
-            img0 = img0.to(device)
+        for batch in loader:
+            if tf is not None:
+                raw, aug, path0 = batch
+                img0 = tf(raw, aug)
+            else:
+                img0, path0 = batch
+                img0 = img0.to(device)
             if opt.bayesian:
                 feats, std2 = [], 0.0
                 for _ in range(opt.T):
@@ -395,13 +452,15 @@ def test(opt):
     opt.continue_train = True                  # build_net then loads <which_epoch>_net.pth
     net = build_net(opt, device)
     data = PairDataset(opt, opt.dataroot, opt.datafile)
-    loader = torch.utils.data.DataLoader(data, shuffle=False, batch_size=opt.batch_size, num_workers=0 if data.synthetic else opt.num_workers)
+    tf = gpu_pipeline(opt, data, device)
+    loader = make_loader(opt, data, tf, shuffle=False, batch_size=opt.batch_size)
     wrong = seen = 0
     with torch.no_grad():
-        for i, (img0, img1, label) in enumerate(loader):
-            out = net(img0.to(device), img1.to(device))
+        for i, batch in enumerate(loader):
+            img0, img1, label = pair_batch(batch, tf, device)
+            out = net(img0, img1)
             prob = torch.sigmoid(out[0] - out[1])          # P(first > second) from the two ratings (every head variant returns them first)
-            wrong += int((predictions(prob, opt.draw_prob_thresh).cpu() != label.reshape(-1)).sum())
+            wrong += int((predictions(prob, opt.draw_prob_thresh).cpu() != label.cpu().reshape(-1)).sum())
             seen += int(label.numel())
             print('--> batch #%d' % (i + 1))
     acc = 100.0 * (1.0 - wrong / max(seen, 1))
