@@ -480,7 +480,49 @@ size_t pcgan_conv2d_wgrad_direct_workspace_bytes(const pcgan_conv_desc* d);
 int pcgan_conv2d_bwd_weight_direct(const pcgan_conv_desc* d, const void* x, const float* x_amax, int n_xamax, const void* dy,
                                    const float* dy_amax, int n_dyamax, float* dw, int accumulate, void* ws, size_t ws_bytes, pcgan_stream_t s);
 
-/* ---- kernel timer (measurement only) -----------------------------------------------------------------------------------------------
+/* ---- Inception-v3 feature network (FID; forward only, fp32 tensors; csrc/inception.hip) ----------------------------------------------
+ * Replaces torchvision's Inception3 blocks behind the reference's models/inception.py (InceptionV3, used by compute_fid_score.py:56-57,
+ * 260-290): BasicConv2d = Conv2d(bias=False) + eval BatchNorm2d(eps=0.001) + ReLU, the InceptionA..E branch pools, and the input
+ * F.upsample(bilinear) + normalize_input of its forward.
+ *
+ * pcgan_iconv_desc: a convolution with PER-AXIS zero padding (1x7, 7x1, 1x3, 3x1 kernels) whose output is channel slice
+ * [k_off, k_off + K) of an NCHW tensor y[N][K_total][P][Q] (a Mixed block's branches write their slices of its output: no concatenation).
+ * R, S <= 7, 0 <= pad_h < R, 0 <= pad_w < S, stride 1 or 2, dtype PCGAN_F32 only (bf16 is refused); pcgan_iconv_supported says whether a
+ * geometry is taken (0: the reason is in pcgan_last_error()).
+ *
+ * pcgan_iconv_pack (once per weight load): w[K][C][R][S] fp32 and the eval BatchNorm's gamma, beta, running mean, running var (all four
+ * given, or all NULL for a plain convolution) folded in fp32 -- w * gamma / sqrt(var + eps), beta - mean * gamma / sqrt(var + eps) -- into
+ * `packed` (pcgan_iconv_packed_bytes(d) bytes, 16-byte aligned): the bias, then the kernel's transposed weight layout.  pool_expand != 0:
+ * w is a 1x1 weight w[K][C][1][1] and d describes the 3x3 pad-1 stride-1 convolution it becomes, every tap w / 9 -- avg_pool2d(3, 1, 1,
+ * count_include_pad=True) then the 1x1 conv, as one linear map (the pool branches of InceptionA / C / E need no pool pass).
+ * pcgan_iconv_fwd: y[:, k_off:k_off+K] = act(conv(x, W') + b'), act = ReLU if relu != 0; channels outside the slice are not touched.
+ * Implicit GEMM on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), no operand scaling; blocked summation (16-term partial sums added
+ * in reduction order).
+ *
+ * pcgan_maxpool_slice_fwd: max_pool2d(k, stride, no padding, floor mode) of x[N][C][H][W] into channels [k_off, k_off + C) of
+ * y[N][K_total][P][Q] (the InceptionB / D pool branches; exact).  Unlike pcgan_maxpool_fwd it writes no argmax.
+ * pcgan_inception_prep: x[N][3][H][W] -> y[N][3][OH][OW], F.interpolate(mode='bilinear', align_corners=False) with ATen's source index
+ * (scale = H / OH in fp32, src = scale * (dst + 0.5) - 0.5 clamped at 0), then y[:, c] = y[:, c] * scale[c] + shift[c] when scale / shift
+ * (host arrays of 3 floats, read at the call) are given.  OH == H, OW == W is the affine alone (the resize is then an exact copy). */
+typedef struct {
+    int N, C, H, W;       /* input  [N][C][H][W]                               */
+    int K, R, S;          /* weight [K][C][R][S]                               */
+    int stride, pad_h, pad_w;
+    int P, Q;             /* output channels [k_off, k_off + K) of [N][K_total][P][Q] */
+    int k_off, K_total;
+    int dtype;            /* PCGAN_F32 only                                    */
+} pcgan_iconv_desc;
+int pcgan_iconv_supported(const pcgan_iconv_desc* d);
+size_t pcgan_iconv_packed_bytes(const pcgan_iconv_desc* d);
+int pcgan_iconv_pack(const pcgan_iconv_desc* d, int pool_expand, const float* w, const float* gamma, const float* beta, const float* mean,
+                     const float* var, float eps, void* packed, pcgan_stream_t s);
+int pcgan_iconv_fwd(const pcgan_iconv_desc* d, const void* x, const void* packed, void* y, int relu, pcgan_stream_t s);
+int pcgan_maxpool_slice_fwd(const void* x, void* y, int N, int C, int H, int W, int k, int stride, int P, int Q, int k_off, int K_total,
+                            int dtype, pcgan_stream_t s);
+int pcgan_inception_prep(const void* x, void* y, int N, int C, int H, int W, int OH, int OW, const float* scale, const float* shift,
+                         int dtype, pcgan_stream_t s);
+
+/* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),
  * whichever entry point issued them.  pcgan_timer_enable(capacity) creates `capacity` event pairs per kind and switches recording on

@@ -32,8 +32,15 @@ class ConvDesc(ctypes.Structure):
                 ('N', 'C', 'H', 'W', 'K', 'R', 'S', 'stride', 'pad', 'pad_mode', 'P', 'Q', 'dtype')]
 
 
+class IconvDesc(ctypes.Structure):
+    """pcgan_iconv_desc (include/pcgan_hip.h): the Inception convolution, per-axis padding, output channel slice"""
+    _fields_ = [(n, ctypes.c_int) for n in
+                ('N', 'C', 'H', 'W', 'K', 'R', 'S', 'stride', 'pad_h', 'pad_w', 'P', 'Q', 'k_off', 'K_total', 'dtype')]
+
+
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _dp = ctypes.POINTER(ConvDesc)
+_icp = ctypes.POINTER(IconvDesc)
 _ip = ctypes.POINTER(ImageDesc)
 _rp = ctypes.POINTER(ResBlockDesc)
 
@@ -144,6 +151,12 @@ SIGNATURES = {
     'pcgan_image_transform': (_i, [_ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'pcgan_image_resize_u8': (_i, [_ip, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'pcgan_image_affine': (_i, [_ip, _vp, _vp, _vp, _vp, _i, _vp]),
+    'pcgan_iconv_supported': (_i, [_icp]),
+    'pcgan_iconv_packed_bytes': (_sz, [_icp]),
+    'pcgan_iconv_pack': (_i, [_icp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    'pcgan_iconv_fwd': (_i, [_icp, _vp, _vp, _vp, _i, _vp]),
+    'pcgan_maxpool_slice_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pcgan_inception_prep': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
 }
 
 _lib = None
