@@ -555,6 +555,19 @@ int pcgan_set_option(const char* key, int value);
 int pcgan_get_option(const char* key, int* value);
 int pcgan_timer_enable(int capacity);
 int pcgan_timer_read(int kind, float* ms, int cap);
+/* Launch record of the implicit-GEMM family (host memory, no synchronisation): what the last forward / data-gradient call of
+ * pcgan_conv2d_fwd* / pcgan_conv2d_bwd_data* that reached the implicit GEMM launched, after every clamp of a forced "hgemm_tile" /
+ * "hgemm_ks".  info[0 .. n) = {sequence number (+1 per recorded launch), form (PCGAN_IGEMM_*), mode (0 forward zero padding, 1 forward
+ * reflection padding, 2 data gradient, 3 data gradient gathering reflection mirrors), BM, BP (0 for the small-M kernels), K split,
+ * phases}; entries past PCGAN_IGEMM_LAUNCH_INFO are 0.  The window / split / thin kernels do not record. */
+#define PCGAN_IGEMM_LAUNCH_INFO 7
+#define PCGAN_IGEMM_HGEMM_F16X2 1  /* hgemm_kernel, fp32 tensors as two scaled fp16 pieces */
+#define PCGAN_IGEMM_HGEMM_BF16 2   /* hgemm_kernel, bf16 tensors, one product */
+#define PCGAN_IGEMM_IGEMM2_CG16 3  /* igemm2_kernel, chunked K order (multiple of 16 gathered channels), fp32 MFMA */
+#define PCGAN_IGEMM_IGEMM2_CG4 4   /* igemm2_kernel, 3- / 4-channel gathered tensor */
+#define PCGAN_IGEMM_GENERIC 5      /* igemm_kernel, generic K order */
+#define PCGAN_IGEMM_SMALLM 6       /* <= 4 output channels, vector ALU */
+int pcgan_igemm_last_launch(int* info, int n);
 
 #ifdef __cplusplus
 }

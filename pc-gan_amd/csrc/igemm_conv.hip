@@ -20,6 +20,7 @@
 // Reference call sites replaced: see include/pcgan_hip.h.
 #include "common.h"
 #include <stdlib.h>
+#include <mutex>
 #include <type_traits>
 
 namespace pcgan {
@@ -2452,6 +2453,17 @@ static void choose_tile(int M, int ptot_max, int nphase, int nst, bool allow_spl
     *bp = p;
 }
 
+// host-side record of the last launch launch_igemm decided (pcgan_igemm_last_launch): kernel form, mode, tile and K split as launched,
+// after every clamp -- a forced hgemm_tile / hgemm_ks may be cut by the shape, so a test reads back which instantiation it checked
+static std::mutex g_launch_mu;
+static int g_launch[PCGAN_IGEMM_LAUNCH_INFO] = {0};
+static void record_launch(int form, int mode, int bm, int bp, int ks, int nphase) {
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    const int seq = g_launch[0] + 1;
+    const int v[PCGAN_IGEMM_LAUNCH_INFO] = {seq, form, mode, bm, bp, ks, nphase};
+    for (int i = 0; i < PCGAN_IGEMM_LAUNCH_INFO; ++i) g_launch[i] = v[i];
+}
+
 template <int MODE>
 static int launch_igemm(IgemmArgs& a, hipStream_t st, float* part_ws = nullptr, size_t part_bytes = 0) {
     int pmax = 0;
@@ -2484,6 +2496,7 @@ static int launch_igemm(IgemmArgs& a, hipStream_t st, float* part_ws = nullptr, 
                 }
                 a.ksplit = ks;
                 a.Ypart = part_ws;
+                record_launch(PCGAN_IGEMM_SMALLM, MODE, 0, 0, ks, a.nphase);
                 const dim3 gs((unsigned)((maxstrips + 63) / 64), (unsigned)a.nphase, (unsigned)ks);
 #define LS(NRV) do { if (a.M <= 3) LAUNCH_TA(a.dtype, smallm_strip_kernel, gs, a, SMODE, NRV, 3); \
                      else LAUNCH_TA(a.dtype, smallm_strip_kernel, gs, a, SMODE, NRV, 4); } while (0)
@@ -2496,6 +2509,7 @@ static int launch_igemm(IgemmArgs& a, hipStream_t st, float* part_ws = nullptr, 
         }
         int maxtaps = 0;
         for (int i = 0; i < a.nphase; ++i) maxtaps = a.ph[i].nR * a.ph[i].nS > maxtaps ? a.ph[i].nR * a.ph[i].nS : maxtaps;
+        record_launch(PCGAN_IGEMM_SMALLM, MODE, 0, 0, 1, a.nphase);
         if (maxtaps <= 9) {
             const dim3 g1((unsigned)((pmax + 255) / 256), (unsigned)a.nphase);
             LAUNCH_TA(a.dtype, smallm_conv_fewtaps_kernel, g1, a, (MODE == MODE_BWD_REFLECT ? MODE_BWD : MODE));
@@ -2537,6 +2551,7 @@ static int launch_igemm(IgemmArgs& a, hipStream_t st, float* part_ws = nullptr, 
     if ((half || (a.hsplit && a.dtype == PCGAN_F32)) && cg16 && MODE != MODE_BWD_REFLECT && bm >= 64) {
         // fp16 two-piece form (fp32 tensors) / bf16 form (bf16 tensors) of the same launch: same tiles, phases, K splits
         constexpr int HMODE = MODE == MODE_BWD_REFLECT ? MODE_BWD : MODE;
+        record_launch(half ? PCGAN_IGEMM_HGEMM_BF16 : PCGAN_IGEMM_HGEMM_F16X2, HMODE, bm, bp, ks, a.nphase);
 #define LH(BMV, BPV) do { if (half) hipLaunchKernelGGL((hgemm_kernel<HMODE, BMV, BPV, bf16>), grid2, dim3(256), 0, st, a); \
                           else hipLaunchKernelGGL((hgemm_kernel<HMODE, BMV, BPV, float>), grid2, dim3(256), 0, st, a); } while (0)
         if (bm == 128 && bp == 128) LH(128, 128);
@@ -2554,6 +2569,8 @@ static int launch_igemm(IgemmArgs& a, hipStream_t st, float* part_ws = nullptr, 
         else if (cg4) LAUNCH_TA(a.dtype, igemm2_kernel, grid2, a, (MODE == MODE_BWD_REFLECT ? MODE_BWD : MODE), BMV, BPV, 4); \
         else LAUNCH_TA(a.dtype, igemm_kernel, grid, a, (MODE == MODE_BWD_REFLECT ? MODE_BWD : MODE), BMV, BPV); \
     } while (0)
+    record_launch(cg16 ? PCGAN_IGEMM_IGEMM2_CG16 : (cg4 ? PCGAN_IGEMM_IGEMM2_CG4 : PCGAN_IGEMM_GENERIC),
+                  (cg16 || MODE != MODE_BWD_REFLECT) ? MODE : MODE_BWD, bm, bp, ks, a.nphase);
     if (bm == 128 && bp == 128) LI(128, 128);
     else if (bm == 128) LI(128, 64);
     else if (bm == 64 && bp == 128) LI(64, 128);
@@ -3011,6 +3028,13 @@ extern "C" int pcgan_conv2d_hgemm_pack(const pcgan_conv_desc* d, int pass, const
         hipLaunchKernelGGL(hgemm_presplit_kernel, dim3(blocks), dim3(256), 0, st, packed + ph[i].off, M, ph[i].kp / 4, (const float*)w_rowmax);
         PCGAN_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+extern "C" int pcgan_igemm_last_launch(int* info, int n) {
+    PCGAN_CHECK(info != nullptr && n > 0, "igemm_last_launch: null output");
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    for (int i = 0; i < n; ++i) info[i] = i < PCGAN_IGEMM_LAUNCH_INFO ? g_launch[i] : 0;
     return 0;
 }
 

@@ -98,19 +98,20 @@ class _ResBlockFn(torch.autograd.Function):
         pack1, pack2 = _pack_cache(w1), _pack_cache(w2)
         out, saved = ops.resblock_fwd(pl, x, w1, b1, w2, b2, in1.running_mean if upd1 else None, in1.running_var if upd1 else None,
                                       in2.running_mean if upd2 else None, in2.running_var if upd2 else None, pack1, pack2)
-        ctx.pl, ctx.saved, ctx.packs, ctx.params = pl, saved, (pack1, pack2), (w1, b1, w2, b2)
-        ctx.save_for_backward(x, w1, w2)
+        ctx.pl, ctx.packs, ctx.params = pl, (pack1, pack2), (w1, b1, w2, b2)
+        # the block's activations go through save_for_backward (not a ctx attribute): autograd frees them right after a backward that
+        # does not retain the graph, and keeps them for one that does -- update_G_and_E back-propagates twice through the generator
+        ctx.save_for_backward(x, w1, w2, *saved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, w1, w2 = ctx.saved_tensors
+        x, w1, w2, *saved = ctx.saved_tensors
         p1, pb1, p2, pb2 = ctx.params
         tw1, tb1, tw2, tb2 = (_fused_grad_target(p) for p in (p1, pb1, p2, pb2))
         assert tw1 is not None and tw2 is not None and (pb1 is None or tb1 is not None) and (pb2 is None or tb2 is not None), \
             'pcgan_amd: the composite residual block needs FusedAdam gradient buffers (checked in forward)'
-        dx = ops.resblock_bwd(ctx.pl, _c(dout), x, ctx.saved, w1, w2, tw1, tb1, tw2, tb2, ctx.packs[0], ctx.packs[1])
-        ctx.saved = None
+        dx = ops.resblock_bwd(ctx.pl, _c(dout), x, tuple(saved), w1, w2, tw1, tb1, tw2, tb2, ctx.packs[0], ctx.packs[1])
         return dx, None, None, None, None, None, None, None
 
 
@@ -161,13 +162,13 @@ class _ResTrunkFn(torch.autograd.Function):
             blocks.append((w1, b1, w2, b2, in1.running_mean if u1 else None, in1.running_var if u1 else None,
                            in2.running_mean if u2 else None, in2.running_var if u2 else None, _pack_cache(w1), _pack_cache(w2)))
         out, saved = ops.restrunk_fwd(pl, x, blocks)
-        ctx.pl, ctx.saved, ctx.params = pl, saved, params
-        ctx.save_for_backward(x)
+        ctx.pl, ctx.params = pl, params
+        ctx.save_for_backward(x, *saved)      # (as in _ResBlockFn: freed after the last backward that uses them, ~1.2 GB at batch 32)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
+        x, *saved = ctx.saved_tensors
         params = ctx.params
         blocks = []
         for i in range(len(params) // 4):
@@ -176,8 +177,7 @@ class _ResTrunkFn(torch.autograd.Function):
             assert t[0] is not None and t[2] is not None and (b1 is None or t[1] is not None) and (b2 is None or t[3] is not None), \
                 'pcgan_amd: the composite residual trunk needs FusedAdam gradient buffers (checked in forward)'
             blocks.append((w1, w2, t[0], t[1], t[2], t[3], _pack_cache(w1), _pack_cache(w2)))
-        dx = ops.restrunk_bwd(ctx.pl, _c(dout), x, ctx.saved, blocks)
-        ctx.saved = None
+        dx = ops.restrunk_bwd(ctx.pl, _c(dout), x, tuple(saved), blocks)
         return (dx, None, None) + (None,) * len(params)
 
 

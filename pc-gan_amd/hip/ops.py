@@ -968,6 +968,20 @@ def timer_read(kind, cap=65536):
     return [float(buf[i]) for i in range(n)]
 
 
+# ---------------------------------------------------------------- implicit-GEMM launch record (tests pin the instantiation they check)
+IGEMM_FORMS = {1: 'hgemm_f16x2', 2: 'hgemm_bf16', 3: 'igemm2_cg16', 4: 'igemm2_cg4', 5: 'igemm', 6: 'smallm'}
+IGEMM_MODES = {0: 'fwd_zero', 1: 'fwd_reflect', 2: 'dgrad', 3: 'dgrad_reflect'}
+
+
+def igemm_last_launch():
+    """what the last implicit-GEMM launch was (pcgan_igemm_last_launch, host memory): {'seq', 'form', 'mode', 'bm', 'bp', 'ks', 'nphase'}
+    with form / mode as names; seq grows by one per recorded launch"""
+    buf = (ctypes.c_int * 7)()
+    _L.check(_L.load().pcgan_igemm_last_launch(buf, 7), 'igemm_last_launch')
+    seq, form, mode, bm, bp, ks, nph = list(buf)
+    return {'seq': seq, 'form': IGEMM_FORMS.get(form), 'mode': IGEMM_MODES.get(mode), 'bm': bm, 'bp': bp, 'ks': ks, 'nphase': nph}
+
+
 # ---------------------------------------------------------------- pointwise
 def channel_sum(x, accumulate_into=None):
     _chk(accumulate_into)

@@ -105,3 +105,13 @@ def test_library_reads_no_environment_and_options_are_explicit():
     assert h.pcgan_set_option(b'no_such_option', 1) != 0 and b'unknown option' in h.pcgan_last_error()
     assert h.pcgan_set_option(b'wgrad_cw', 77) != 0
     assert h.pcgan_set_option(b'hgemm_tile', 96096) != 0 and h.pcgan_set_option(b'hgemm_ks', 9) != 0
+
+
+def test_igemm_launch_record_query():
+    """pcgan_igemm_last_launch reads host memory only (callable without a GPU): entries past the record are 0, a null output is refused"""
+    import ctypes
+    from pcgan_amd.hip import lib
+    h = lib.load()
+    buf = (ctypes.c_int * 9)(*([-1] * 9))
+    assert h.pcgan_igemm_last_launch(buf, 9) == 0 and list(buf)[7:] == [0, 0] and min(buf) >= 0
+    assert h.pcgan_igemm_last_launch(None, 7) != 0 and b'igemm_last_launch' in h.pcgan_last_error()

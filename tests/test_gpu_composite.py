@@ -142,6 +142,57 @@ def test_full_size_step_composite_equals_per_op(tmp_path, dev, monkeypatch):
             assert torch.equal(a['bufs'][k], b['bufs'][k]), k
 
 
+def test_full_size_lr_E_step_composite_equals_per_op(tmp_path, dev, monkeypatch):
+    """`--lr_E > 0` on the config-2 networks (as test_full_size_step_composite_equals_per_op): update_G_and_E back-propagates loss_G with
+    retain_graph=True, steps G and E, then back-propagates the rating reconstruction through the RETAINED graph of fake_B -- a second
+    backward through the trunk / block nodes, which must still hold the activations their first backward read.  Trunk, per-block
+    composite and per-op: G / D / E parameters, images, losses and running statistics bit-identical; the retained pass provably ran
+    through the trunk node (three trunk backwards per step: two generator passes, then fake_B's again)."""
+    import sys
+    import bench
+    from pcgan_amd.hip import ops
+    from pcgan_amd.options.train_options import TrainOptions
+    monkeypatch.setattr(ops, 'BSPLIT_MIN_PIXELS', 0)
+    parse = TrainOptions.parse
+
+    def parse_lr_E(self):          # bench.build_model's networks and options, with the encoder training inside the step
+        sys.argv = sys.argv + ['--lr_E', '0.0001']
+        return parse(self)
+    monkeypatch.setattr(TrainOptions, 'parse', parse_lr_E)
+    res = []
+    for comp, trunk in ((True, True), (True, False), (False, False)):
+        monkeypatch.setattr(ops, 'COMPOSITE', comp)
+        monkeypatch.setattr(ops, 'TRUNK', trunk)
+        before = dict(ops.COMPOSITE_STATS)
+        torch.manual_seed(0)
+        tmp = tmp_path / ('lr_E%d%d' % (int(comp), int(trunk)))
+        tmp.mkdir()
+        model, opt = bench.build_model(0, 2, 128, str(tmp), seed=3)
+        assert opt.lr_E > 0 and opt.lambda_z > 0 and model.optimizer_E in model.optimizers
+        for it in range(2):
+            model.set_input(bench.synthetic_batch(2, 128, 0, it))
+            model.optimize_parameters()
+        torch.cuda.synchronize()
+        took = ops.COMPOSITE_STATS['fwd'] - before['fwd'], ops.COMPOSITE_STATS['bwd'] - before['bwd']
+        assert took == ((2 * 2 * 9, 2 * 3 * 9) if comp else (0, 0)), took
+        trunks = ops.COMPOSITE_STATS.get('trunk_fwd', 0) - before.get('trunk_fwd', 0), ops.COMPOSITE_STATS.get('trunk_bwd', 0) - before.get('trunk_bwd', 0)
+        assert trunks == ((4, 6) if trunk else (0, 0)), trunks
+        res.append({'G': model.optimizer_G.flat.detach().clone(), 'D': model.optimizer_D.flat.detach().clone(),
+                    'E': model.optimizer_E.flat.detach().clone(), 'fake_B': model.fake_B.detach().clone(), 'rec_A': model.rec_A.detach().clone(),
+                    'losses': dict(model.get_current_losses()),
+                    'bufs': {n + '.' + k: v.detach().clone() for n in ('G', 'E') for k, v in getattr(model, 'net' + n).state_dict().items()
+                             if 'running' in k}})
+        del model
+    for b in res[1:]:
+        a = res[0]
+        for k in ('G', 'D', 'E', 'fake_B', 'rec_A'):
+            assert torch.equal(a[k], b[k]), k
+        assert a['losses'] == b['losses']
+        assert a['bufs'].keys() == b['bufs'].keys() and len(a['bufs']) > 0
+        for k in a['bufs']:
+            assert torch.equal(a['bufs'][k], b['bufs'][k]), k
+
+
 @pytest.mark.parametrize('nb,N,H,dt', [(3, 4, 32, 'fp32'), (9, 32, 32, 'fp32'), (2, 2, 64, 'fp32'), (3, 4, 32, 'bf16'), (9, 32, 32, 'bf16')])
 def test_restrunk_is_the_chain_of_block_calls(dev, monkeypatch, nb, N, H, dt):
     """pcgan_restrunk_fwd / _bwd on a chain of nb ResnetBlocks inside an nn.Sequential (as in ResnetGenerator): output, input gradient,
