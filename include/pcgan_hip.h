@@ -522,6 +522,17 @@ int pcgan_maxpool_slice_fwd(const void* x, void* y, int N, int C, int H, int W, 
 int pcgan_inception_prep(const void* x, void* y, int N, int C, int H, int W, int OH, int OW, const float* scale, const float* shift,
                          int dtype, pcgan_stream_t s);
 
+/* ---- classifier head of the Inception Score (forward only, fp32 tensors; csrc/inception.hip) ------------------------------------------
+ * logits[N][K] = x[N][C] W[K][C]^T + b[K] (nn.Linear's layout; b may be NULL) and probs[N][K] = softmax(logits, dim=1).  Replaces
+ *   F.softmax(inception_model(x))   util/inception_score.py:38-41 (torchvision inception_v3's fc, then the softmax)
+ *   nn.Linear                       models/resnet.py:194 (the fc of the networks.ResNet classifier, models/networks.py:1258-1285)
+ * Any N, C, K >= 1.  fp32 accumulation in a fixed order (exact-fp32 MFMA chains over four interleaved quarters of C, the four partial
+ * sums added in order, then the bias); softmax = expf(l - row max) / fixed-order row sum, full-precision expf: results are bit-identical
+ * from run to run and beside other streams' work (no atomics).  Each workgroup reads its tile of W once per batch tile of 64 rows.
+ * logits may be NULL (they are then staged in probs).  dtype PCGAN_F32 only. */
+int pcgan_linear_softmax_fwd(const void* x, const float* w, const float* b, void* logits, void* probs, int N, int C, int K, int dtype,
+                             pcgan_stream_t s);
+
 /* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),

@@ -11,6 +11,7 @@
 //                  count_include_pad=True) followed by a 1x1 conv is exactly that linear map.
 //   maxpool_slice  max pool (no padding, floor mode) into a channel slice (the InceptionB / D pool branches).
 //   inception_prep bilinear resize (align_corners=False, ATen's source-index rule) + per-channel affine, one pass.
+//   linear_fwd + softmax_rows   the classifier head of the Inception Score: nn.Linear on the exact-fp32 MFMA, then a row softmax.
 #include "common.h"
 #include <float.h>
 
@@ -228,6 +229,110 @@ static inline int ew_grid(size_t n) {
     return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
+// ---- classifier head: logits = x W^T + b, probs = softmax(logits, dim=1) --------------------------------------------------------------
+// The op is bound by W (8 MB at K = 1000, C = 2048), not by its arithmetic, so one workgroup owns a tile of LS_KT classes and a batch
+// tile of LS_NB rows and reads its W tile once for all of them.  The four waves split the reduction: wave w takes the 16-wide chunks
+// w, w + 4, w + 8, ... of C (exact-fp32 v_mfma_f32_16x16x4_f32, a k-ordered fma chain), and the four partial sums meet in LDS, added in
+// wave order.  No atomics: every result has one fixed summation order, whatever runs beside it.
+constexpr int LS_KT = 16;        // classes per workgroup (the MFMA's 16 columns)
+constexpr int LS_NB = 64;        // rows per workgroup (four 16-row MFMA tiles)
+constexpr int LS_WAVES = 4;
+constexpr int LS_THREADS = 64 * LS_WAVES;
+constexpr int SM_THREADS = 256;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// 4 consecutive elements row[c .. c + 3], zeros past C or for a row outside the tensor; vec: 16-byte loads (C % 4 == 0, aligned rows)
+__device__ __forceinline__ float4 ls_load4(const float* __restrict__ row, bool row_ok, int c, int C, bool vec) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!row_ok || c >= C) return v;
+    if (vec) return *reinterpret_cast<const float4*>(row + c);
+    v.x = row[c];
+    if (c + 1 < C) v.y = row[c + 1];
+    if (c + 2 < C) v.z = row[c + 2];
+    if (c + 3 < C) v.w = row[c + 3];
+    return v;
+}
+
+__global__ void __launch_bounds__(LS_THREADS) linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ b, float* __restrict__ y, int N, int C,
+                                                                int K, int vec) {
+    __shared__ float part[LS_WAVES][LS_NB * LS_KT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int k0 = blockIdx.x * LS_KT, n0 = blockIdx.y * LS_NB;
+    const int col = lane & 15, kq = (lane >> 4) * 4;   // operand lanes: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15]
+    const bool vec4 = vec != 0;
+
+    const bool w_ok = k0 + col < K;
+    const float* wrow = w + (size_t)(w_ok ? k0 + col : 0) * C;
+    const float* xrow[LS_NB / 16];
+    bool x_ok[LS_NB / 16];
+#pragma unroll
+    for (int s = 0; s < LS_NB / 16; ++s) {
+        const int n = n0 + 16 * s + col;
+        x_ok[s] = n < N;
+        xrow[s] = x + (size_t)(x_ok[s] ? n : 0) * C;
+    }
+
+    f32x4 acc[LS_NB / 16];
+#pragma unroll
+    for (int s = 0; s < LS_NB / 16; ++s) acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // lane l holds elements c0 + kq .. + 3 of its rows; MFMA t multiplies element t, so the four k slots of one instruction are
+    // c0 + t, c0 + 4 + t, c0 + 8 + t, c0 + 12 + t (A and B alike)
+    for (int c0 = 16 * wave; c0 < C; c0 += 16 * LS_WAVES) {
+        const float4 wv = ls_load4(wrow, w_ok, c0 + kq, C, vec4);
+        float4 xv[LS_NB / 16];
+#pragma unroll
+        for (int s = 0; s < LS_NB / 16; ++s) xv[s] = ls_load4(xrow[s], x_ok[s], c0 + kq, C, vec4);
+#pragma unroll
+        for (int s = 0; s < LS_NB / 16; ++s) {
+            acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[s].x, wv.x, acc[s], 0, 0, 0);
+            acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[s].y, wv.y, acc[s], 0, 0, 0);
+            acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[s].z, wv.z, acc[s], 0, 0, 0);
+            acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[s].w, wv.w, acc[s], 0, 0, 0);
+        }
+    }
+
+    // D[i][j]: lane l, register r holds row (l >> 4) * 4 + r, column l & 15
+#pragma unroll
+    for (int s = 0; s < LS_NB / 16; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[wave][(16 * s + kq + r) * LS_KT + col] = acc[s][r];
+    __syncthreads();
+    for (int e = tid; e < LS_NB * LS_KT; e += LS_THREADS) {
+        const int n = n0 + e / LS_KT, k = k0 + e % LS_KT;
+        if (n >= N || k >= K) continue;
+        float v = part[0][e];
+#pragma unroll
+        for (int q = 1; q < LS_WAVES; ++q) v += part[q][e];
+        if (b) v += b[k];
+        y[(size_t)n * K + k] = v;
+    }
+}
+
+// one workgroup per row: p = exp(l - max) / sum, full-precision expf, the sum in a fixed order (each thread's elements in index order,
+// then the wave butterfly, then the waves in order).  src may be dst (the logits were staged in the probability buffer).
+__global__ void __launch_bounds__(SM_THREADS) softmax_rows_kernel(const float* src, float* dst, int K) {
+    __shared__ float scratch[SM_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* l = src + (size_t)blockIdx.x * K;
+    float* p = dst + (size_t)blockIdx.x * K;
+    float m = -INFINITY;
+    for (int i = tid; i < K; i += SM_THREADS) m = fmaxf(m, l[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) scratch[wave] = m;
+    __syncthreads();
+    m = scratch[0];
+#pragma unroll
+    for (int q = 1; q < SM_THREADS / 64; ++q) m = fmaxf(m, scratch[q]);
+    float s = 0.f;
+    for (int i = tid; i < K; i += SM_THREADS) s += expf(l[i] - m);
+    s = block_sum(s, scratch);     // barrier first: every thread has read the row maximum from scratch
+    for (int i = tid; i < K; i += SM_THREADS) p[i] = expf(l[i] - m) / s;
+}
+
 }  // namespace
 
 // geometry check shared by the queries and the launches; sets the error text
@@ -355,6 +460,24 @@ extern "C" int pcgan_inception_prep(const void* x, void* y, int N, int C, int H,
     hipLaunchKernelGGL(inception_prep_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)s, (const float*)x, (float*)y, H, W, OH,
                        OW, rh, rw, scale ? 1 : 0, scale ? scale[0] : 1.f, scale ? scale[1] : 1.f, scale ? scale[2] : 1.f,
                        shift ? shift[0] : 0.f, shift ? shift[1] : 0.f, shift ? shift[2] : 0.f, total);
+    PCGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pcgan_linear_softmax_fwd(const void* x, const float* w, const float* b, void* logits, void* probs, int N, int C, int K,
+                                        int dtype, pcgan_stream_t s) {
+    PCGAN_CHECK(dtype == PCGAN_F32, "linear_softmax_fwd: fp32 tensors only (dtype %d)", dtype);
+    PCGAN_CHECK(N > 0 && C > 0 && K > 0, "linear_softmax_fwd: non-positive size (N %d C %d K %d)", N, C, K);
+    PCGAN_CHECK(x && w && probs, "linear_softmax_fwd: null x / w / probs");
+    PCGAN_CHECK((N + LS_NB - 1) / LS_NB <= 65535, "linear_softmax_fwd: N %d too large (at most %d rows)", N, 65535 * LS_NB);
+    const size_t addr = reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(w);
+    const int vec = (C % 4 == 0 && (addr & 15) == 0) ? 1 : 0;
+    // without a logits buffer the logits are staged in probs and the softmax runs in place
+    float* lg = logits ? (float*)logits : (float*)probs;
+    const dim3 grid((K + LS_KT - 1) / LS_KT, (N + LS_NB - 1) / LS_NB);
+    hipLaunchKernelGGL(linear_fwd_kernel, grid, dim3(LS_THREADS), 0, (hipStream_t)s, (const float*)x, w, b, lg, N, C, K, vec);
+    PCGAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_rows_kernel, dim3(N), dim3(SM_THREADS), 0, (hipStream_t)s, (const float*)lg, (float*)probs, K);
     PCGAN_LAUNCH_CHECK();
     return 0;
 }

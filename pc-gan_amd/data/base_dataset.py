@@ -105,33 +105,42 @@ def get_transform(opt):
     """PIL.Image -> float tensor (3, H, W) in [-1, 1]: every `--transforms` mode of the reference (data/base_dataset.py:24-64).
     `--use_color_jitter` adds transforms.ColorJitter() with its default arguments (brightness = contrast = saturation = hue = 0):
     the identity, so the flag is accepted and changes nothing -- as in the reference."""
-    from PIL import Image
     if opt.transforms not in TRANSFORM_MODES:
         raise ValueError('--resize_or_crop %s is not a valid option.' % opt.transforms)
 
     def tf(img):
-        w, h = img.size
-        resized, fs, centre = resize_plan(opt, w, h)
-        if resized is not None:
-            img = img.resize(resized, Image.BICUBIC)
-        if opt.transforms in ('resize_affine_crop', 'resize_affine_center'):
-            img = random_affine(img, opt.affineDegrees, tuple(opt.affineScale))
-        if fs is not None:
-            w, h = img.size
-            if w < fs or h < fs:    # torchvision's RandomCrop refuses too (no pad_if_needed in the reference's pipeline)
-                raise ValueError('Required crop size %s is larger than input image size %s' % ((fs, fs), (h, w)))
-            if centre:              # transforms.CenterCrop: round((size - crop) / 2)
-                x0, y0 = int(round((w - fs) / 2.0)), int(round((h - fs) / 2.0))
-            else:
-                x0 = random.randint(0, w - fs) if w > fs else 0
-                y0 = random.randint(0, h - fs) if h > fs else 0
-            img = img.crop((x0, y0, x0 + fs, y0 + fs))
-        if opt.isTrain and not opt.no_flip and random.random() < 0.5:
-            img = img.transpose(Image.FLIP_LEFT_RIGHT)
-        arr = np.asarray(img, dtype=np.float32) / 255.0
-        t = torch.from_numpy(arr.transpose(2, 0, 1).copy())
-        return (t - 0.5) / 0.5
+        return (to_tensor(pil_steps(opt, img)) - 0.5) / 0.5
     return tf
+
+
+def pil_steps(opt, img):
+    """the PIL part of get_transform: the resize, affine warp, crop and (training) flip `--transforms` asks for, drawn from `random`"""
+    from PIL import Image
+    w, h = img.size
+    resized, fs, centre = resize_plan(opt, w, h)
+    if resized is not None:
+        img = img.resize(resized, Image.BICUBIC)
+    if opt.transforms in ('resize_affine_crop', 'resize_affine_center'):
+        img = random_affine(img, opt.affineDegrees, tuple(opt.affineScale))
+    if fs is not None:
+        w, h = img.size
+        if w < fs or h < fs:    # torchvision's RandomCrop refuses too (no pad_if_needed in the reference's pipeline)
+            raise ValueError('Required crop size %s is larger than input image size %s' % ((fs, fs), (h, w)))
+        if centre:              # transforms.CenterCrop: round((size - crop) / 2)
+            x0, y0 = int(round((w - fs) / 2.0)), int(round((h - fs) / 2.0))
+        else:
+            x0 = random.randint(0, w - fs) if w > fs else 0
+            y0 = random.randint(0, h - fs) if h > fs else 0
+        img = img.crop((x0, y0, x0 + fs, y0 + fs))
+    if opt.isTrain and not opt.no_flip and random.random() < 0.5:
+        img = img.transpose(Image.FLIP_LEFT_RIGHT)
+    return img
+
+
+def to_tensor(img):
+    """transforms.ToTensor of an RGB PIL image: (3, H, W) float32 in [0, 1]"""
+    arr = np.asarray(img, dtype=np.float32) / 255.0
+    return torch.from_numpy(arr.transpose(2, 0, 1).copy())
 
 
 AFFINE_MODES = ('resize_affine_crop', 'resize_affine_center')

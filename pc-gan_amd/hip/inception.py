@@ -103,6 +103,24 @@ def prep(x, size=None, scale=None, shift=None):
     return y
 
 
+def linear_softmax(x, w, b=None, want_logits=True):
+    """(logits, probs) = (x w^T + b, softmax(logits, dim=1)) through pcgan_linear_softmax_fwd: x (N, C), w (K, C) and b (K,) or None in
+    nn.Linear's layout.  want_logits=False: logits is None (the kernel stages them in the probability buffer)."""
+    _f32(x, w, b)
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or (b is not None and tuple(b.shape) != (w.shape[0],)):
+        raise RuntimeError('linear_softmax: x %s, w %s, b %s do not form nn.Linear(C -> K) of (N, C) rows'
+                           % (tuple(x.shape), tuple(w.shape), None if b is None else tuple(b.shape)))
+    if w.device != x.device or (b is not None and b.device != x.device):
+        raise RuntimeError('linear_softmax: x, w and b must be on one device')
+    N, C = x.shape
+    K = w.shape[0]
+    probs = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    logits = torch.empty_like(probs) if want_logits else None
+    _L.check(_L.load().pcgan_linear_softmax_fwd(_p(x), _p(w), _p(b), _p(logits), _p(probs), N, C, K, F32, _stream()),
+             'linear_softmax_fwd')
+    return logits, probs
+
+
 def global_avg_pool(x):
     """AdaptiveAvgPool2d(1) through pcgan_global_pool_fwd"""
     _f32(x)

@@ -158,6 +158,7 @@ SIGNATURES = {
     'pcgan_iconv_fwd': (_i, [_icp, _vp, _vp, _vp, _i, _vp]),
     'pcgan_maxpool_slice_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pcgan_inception_prep': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'pcgan_linear_softmax_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -130,6 +130,20 @@ def check_state_dict(sd):
     return {k: sd[k] for k in want}
 
 
+def check_classifier_state_dict(sd):
+    """check_state_dict plus the classifier head of torchvision's inception_v3 (host only, before any device use): fc.weight
+    (classes, 2048) and fc.bias (classes,); returns the number of classes"""
+    check_state_dict(sd)
+    w, b = sd.get('fc.weight'), sd.get('fc.bias')
+    if w is None or b is None:
+        raise KeyError('Inception weights: no fc.weight / fc.bias -- the Inception Score needs the classifier head of torchvision\'s '
+                       'inception_v3 (fc: 2048 -> 1000), not only the feature path')
+    if not (torch.is_tensor(w) and torch.is_tensor(b)) or w.dim() != 2 or w.shape[1] != 2048 or tuple(b.shape) != (w.shape[0],):
+        raise ValueError('Inception weights: fc.weight %s / fc.bias %s, expected (classes, 2048) / (classes,)'
+                         % (tuple(getattr(w, 'shape', ())), tuple(getattr(b, 'shape', ()))))
+    return int(w.shape[0])
+
+
 def load_state_dict_file(weights):
     if isinstance(weights, dict):
         return weights
@@ -254,3 +268,35 @@ class InceptionV3(object):
                 if idx in self.output_blocks:
                     outp.append(x)
         return outp
+
+
+class InceptionV3Classifier(InceptionV3):
+    """torchvision's inception_v3(transform_input=False) in eval mode, as the reference's Inception Score runs it
+    (compute_inception_score.py:28-30, util/inception_score.py:37-41): blocks 0-3 of InceptionV3, dropout (the identity in eval mode),
+    then fc 2048 -> classes and the softmax in one HIP call (pcgan_linear_softmax_fwd).  The input pass only resizes to 299 x 299 by
+    default: the dataset transform has normalised the images already.  The weights file must hold fc.weight / fc.bias."""
+
+    def __init__(self, weights=None, resize_input=True, normalize_input=False, gpu_ids=[0]):
+        self.fc_weight = self.fc_bias = None
+        self.num_classes = None
+        super().__init__([InceptionV3.DEFAULT_BLOCK_INDEX], resize_input, normalize_input, weights, gpu_ids)
+
+    def load_state_dict(self, weights):
+        sd = load_state_dict_file(weights)
+        classes = check_classifier_state_dict(sd)
+        InceptionV3.load_state_dict(self, sd)
+        with torch.cuda.device(self.device), torch.no_grad():
+            self.fc_weight = sd['fc.weight'].detach().to(self.device, torch.float32).contiguous()
+            self.fc_bias = sd['fc.bias'].detach().to(self.device, torch.float32).contiguous()
+        self.num_classes = classes
+        return self
+
+    def __call__(self, x, probs=False):
+        return self.forward(x, probs)
+
+    def forward(self, inp, probs=False):
+        """logits (N, classes); with probs=True (logits, softmax probabilities)"""
+        pooled = InceptionV3.forward(self, inp)[0]
+        with torch.no_grad(), torch.cuda.device(self.device):
+            logits, p = I.linear_softmax(pooled.flatten(1), self.fc_weight, self.fc_bias)
+        return (logits, p) if probs else logits

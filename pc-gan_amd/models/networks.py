@@ -509,3 +509,28 @@ class Normalize(tnn.Module):
 
     def forward(self, input):
         return input
+
+
+class ResNet(tnn.Module):
+    """The reference's classifier wrapper (models/networks.py:1258-1285) that classification.py trains and the Inception Score loads
+    (compute_inception_score.py:31-36): state_dict keys model.conv1.weight ... model.fc.bias.  forward runs the HIP trunk (eval-mode
+    BatchNorm after .eval()), the global average pool and the classifier head kernel (pcgan_linear_softmax_fwd); forward only.
+    resnet101 / resnet152 are outside the HIP path."""
+
+    def __init__(self, input_nc=3, num_classes=0, which_model='resnet18', pretrained=False, dropout=0.):
+        super().__init__()
+        from . import resnet
+        table = {'resnet18': resnet.resnet18, 'resnet34': resnet.resnet34, 'resnet50': resnet.resnet50}
+        if which_model not in table:
+            raise NotImplementedError('pcgan_amd: classifier [%s] is outside the HIP path (resnet18, resnet34, resnet50)' % which_model)
+        self.model = table[which_model](pretrained, num_classes=num_classes, dropout=dropout)
+
+    def forward(self, x, probs=False):
+        """logits (N, num_classes); with probs=True (logits, softmax probabilities)"""
+        from ..hip import inception as I
+        if x.requires_grad:
+            raise RuntimeError('networks.ResNet (HIP) is forward-only: the input requires grad and the head has no backward pass')
+        with torch.no_grad():
+            pooled = I.global_avg_pool(self.model.features(x)).flatten(1)
+            logits, p = I.linear_softmax(pooled, self.model.fc.weight, self.model.fc.bias)
+        return (logits, p) if probs else logits
