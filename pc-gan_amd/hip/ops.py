@@ -336,7 +336,7 @@ PASS_BWD_THIN = 107
 # products (csrc/bf16x6_conv.hip, "fp16 route"); 'bf16' = three bf16 pieces, six products.  Same measured error, half the MFMAs.
 HSPLIT = os.environ.get('PCGAN_SPLIT', 'f16') == 'f16'
 # ... and whether every other convolution with a multiple of 16 gathered channels runs the fp16 two-piece form of the packed
-# implicit GEMM (csrc/igemm_conv.hip hgemm_kernel) instead of the fp32 MFMA one
+# implicit GEMM (csrc/hgemm.hip hgemm_kernel) instead of the fp32 MFMA one
 HGEMM = os.environ.get('PCGAN_HGEMM', '1') == '1'
 # ... and the convolutions that gather <= 4 channels the window kernel of csrc/thin_conv.hip instead of igemm2_kernel<.., 4> on fp32 MFMA
 THIN = os.environ.get('PCGAN_THIN', '1') == '1'

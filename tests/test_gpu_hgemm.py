@@ -1,4 +1,4 @@
-"""The packed implicit GEMM on the matrix pipe (csrc/igemm_conv.hip hgemm_kernel) held to float64, instantiation by instantiation.
+"""The packed implicit GEMM on the matrix pipe (csrc/hgemm.hip hgemm_kernel) held to float64, instantiation by instantiation.
 
 hgemm_kernel is the forward and data-gradient route of every fp32 convolution with a multiple of 16 gathered channels outside the
 residual trunk (two scaled fp16 pieces, three products) and of the same layers for bf16 tensors (one bf16 product).  It comes in four
@@ -42,7 +42,7 @@ def force_hgemm():
 
 
 def _nphase(H, W, k, stride, pad):
-    """data gradient: the (y mod stride, x mod stride) phases that own taps (csrc/igemm_conv.hip conv2d_bwd_data_impl)"""
+    """data gradient: the (y mod stride, x mod stride) phases that own taps (csrc/igemm_conv.hip bwd_plan)"""
     n = 0
     for fy in range(stride):
         for fx in range(stride):

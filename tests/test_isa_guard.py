@@ -4,18 +4,18 @@ Round 3 found one kernel whose sums differed from run to run beside f16-MFMA ker
 (scripts/micro/head_wgrad_isa.md) excluded a compiler wait-count bug and isolated the one instruction form unique to the failing
 build: packed fp32 arithmetic with `op_sel:[0,1,0]` (high dword of src1 broadcast to both lanes).  The cause is not established, so the
 form is banned from the library: this test fails if any kernel contains it."""
-import glob
 import os
 import re
 import shutil
-import subprocess
+import sys
 import tempfile
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, 'pc-gan_amd', 'lib', 'libpcgan_hip.so')
-OBJDUMP = '/opt/rocm/lib/llvm/bin/llvm-objdump'
+sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+from isa_diff import OBJDUMP, code_objects, instructions      # noqa: E402  (the extract-and-disassemble walk, shared with the script)
 
 
 @pytest.mark.timeout(600)
@@ -24,27 +24,17 @@ def test_no_packed_fp32_high_broadcast_form_in_the_library():
         pytest.skip('library or llvm-objdump not present (build() first)')
     tmp = tempfile.mkdtemp(prefix='pcgan_isa_')
     try:
-        work = os.path.join(tmp, 'lib.so')
-        shutil.copy(LIB, work)
-        subprocess.run([OBJDUMP, '--offloading', work], cwd=tmp, check=True, capture_output=True)
-        objs = glob.glob(work + '.*gfx950*')
+        objs = code_objects(LIB, tmp)
         assert objs, 'no gfx950 code object in the library'
         bad, packed, kernels = [], 0, set()
         for o in objs:
-            cur = None
-            p = subprocess.Popen([OBJDUMP, '-d', o], stdout=subprocess.PIPE, text=True)
-            for line in p.stdout:
-                m = re.match(r'^[0-9a-f]+ <(.+)>:', line)
-                if m:
-                    cur = m.group(1)
-                    continue
+            for cur, line in instructions(o):
                 if 'v_pk_' in line and '_f32' in line:
                     packed += 1
                     kernels.add(cur)
                     code = line.split('//')[0]
                     if re.search(r'op_sel:\[0,1,0\]', code) and 'op_sel_hi' not in code:
                         bad.append((cur, code.strip()))
-            p.wait()
         assert packed > 0, 'disassembly found no packed fp32 instruction at all: the scan is broken'
         assert not bad, 'packed fp32 op_sel:[0,1,0] form (scripts/micro/head_wgrad_isa.md) in: %s' % sorted({b[0] for b in bad})[:5]
     finally:
@@ -61,22 +51,12 @@ def test_row_ring_kernels_keep_scalar_loads_out_of_their_stage_loops():
         pytest.skip('library or llvm-objdump not present (build() first)')
     tmp = tempfile.mkdtemp(prefix='pcgan_isa_')
     try:
-        work = os.path.join(tmp, 'lib.so')
-        shutil.copy(LIB, work)
-        subprocess.run([OBJDUMP, '--offloading', work], cwd=tmp, check=True, capture_output=True)
         seen = {}
-        for o in glob.glob(work + '.*gfx950*'):
-            cur = None
-            p = subprocess.Popen([OBJDUMP, '-d', o], stdout=subprocess.PIPE, text=True)
-            for line in p.stdout:
-                m = re.match(r'^[0-9a-f]+ <(.+)>:', line)
-                if m:
-                    cur = m.group(1) if 'rowring_wgrad' in m.group(1) else None
-                    if cur:
-                        seen[cur] = {'mfma': False, 'late_sload': [], 'waits': set()}
+        for o in code_objects(LIB, tmp):
+            for cur, line in instructions(o):
+                if cur is None or 'rowring_wgrad' not in cur:
                     continue
-                if cur is None:
-                    continue
+                seen.setdefault(cur, {'mfma': False, 'late_sload': [], 'waits': set()})
                 code = line.split('//')[0]
                 if 'v_mfma' in code:
                     seen[cur]['mfma'] = True
@@ -85,7 +65,6 @@ def test_row_ring_kernels_keep_scalar_loads_out_of_their_stage_loops():
                 w = re.search(r's_waitcnt lgkmcnt\((\d+)\)\s*$', code.strip())
                 if w:
                     seen[cur]['waits'].add(int(w.group(1)))
-            p.wait()
         assert len(seen) == 2, 'expected the fp32 and the bf16 row-ring kernel, found %r' % sorted(seen)
         for k, v in seen.items():
             assert v['mfma'] and not v['late_sload'], '%s: scalar loads behind the first MFMA: %r' % (k, v['late_sload'][:3])
