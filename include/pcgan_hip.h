@@ -533,6 +533,37 @@ int pcgan_inception_prep(const void* x, void* y, int N, int C, int H, int W, int
 int pcgan_linear_softmax_fwd(const void* x, const float* w, const float* b, void* logits, void* probs, int N, int C, int K, int dtype,
                              pcgan_stream_t s);
 
+/* ---- training pass of the attribute classifier's head (fp32 tensors; csrc/linear_head.hip) --------------------------------------------
+ * nn.Linear(C -> K) + nn.CrossEntropyLoss(weight) of the classifier classification.py trains.  Replaces
+ *   output = net.forward(img0); loss = criterion(output, label); get_prediction(output)     classification.py:330-332, 376-384
+ *   the fc layer at the end of self.model(x)                                                  models/networks.py:1284-1285
+ * Sizes: 1 <= N <= 512 rows, C a multiple of 4 in [4, 2048], 1 <= K <= 1024 classes; dtype PCGAN_F32 only (the head stays fp32 beside
+ * bf16 activations, as losses and statistics do).  Every sum runs in a fixed order in float64 and is rounded to fp32 once: results are
+ * bit-identical from run to run, no float atomics.  x / w / dx / dw that are 16-byte aligned are accessed 128 bits at a time.
+ *
+ * pcgan_linear_ce_fwd, ONE launch of N workgroups:
+ *   logits[n][k]  = sum_c x[n][c] w[k][c] + b[k]                       (b may be NULL)
+ *   loss          = sum_n wt[y_n] (-log_softmax(logits[n])[y_n]) / sum_n wt[y_n]     (row maximum subtracted; class_weight NULL = ones)
+ *   dlogits[n][k] = wt[y_n] (softmax(logits[n])[k] - [k == y_n]) / sum_n wt[y_n]     (d loss / d logits)
+ *   pred[n]       = index of the FIRST maximum of the fp32 logits[n] (numpy.argmax);  correct = #{n : pred[n] == y_n}
+ * labels are int64 DEVICE memory, so they are not checked on the host: a label outside [0, K) never indexes anything on the device -- its
+ * row is ignored (weight 0: no loss term, zero gradient, never counted correct), as ignore_index rows are in torch.  All rows ignored
+ * gives 0 / 0 = NaN, as torch does.  logits, dlogits, loss, pred and correct may each be NULL (not wanted).
+ * workspace: pcgan_linear_ce_workspace_bytes(N) bytes (0: N out of range), 8-byte aligned, caller-owned.  Its first word is the arrival
+ * ticket of the last-arriver reduction of loss / correct: it must be ZERO before the first call and is left zero by every call, so calls
+ * in stream order may share it whatever their N; calls on different streams need one each.
+ *
+ * pcgan_linear_bwd, ONE launch of N + K workgroups:
+ *   dx[n][c] = sum_k dlogits[n][k] w[k][c];   dw[k][c] (+)= sum_n dlogits[n][k] x[n][c];   db[k] (+)= sum_n dlogits[n][k]
+ * accumulate != 0 adds dw / db to what the buffers hold (a FusedAdam gradient buffer), else overwrites; dx is always overwritten.  Any of
+ * dx, dw, db may be NULL, not all three. */
+size_t pcgan_linear_ce_workspace_bytes(int N);
+int pcgan_linear_ce_fwd(const void* x, const float* w, const float* b, const int64_t* labels, const float* class_weight, void* logits,
+                        void* dlogits, float* loss, int64_t* pred, int32_t* correct, void* workspace, size_t workspace_bytes, int N,
+                        int C, int K, int dtype, pcgan_stream_t s);
+int pcgan_linear_bwd(const void* dlogits, const void* x, const float* w, void* dx, float* dw, float* db, int N, int C, int K,
+                     int accumulate, int dtype, pcgan_stream_t s);
+
 /* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),

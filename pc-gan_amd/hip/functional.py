@@ -583,6 +583,69 @@ class _LossFn(torch.autograd.Function):
         return None, ops.scale(grad, _c(dl).reshape(1)), None
 
 
+# ---------------------------------------------------------------------------- classifier head (training pass)
+def _linear_backward(ctx, dlogits, x, w):
+    """(dx, dw, db) of the head for autograd: dw / db go straight into the FusedAdam gradient buffer when both parameters have one
+    (autograd then receives None for them, as in _Conv2dFn.backward)"""
+    pw, pb = ctx.params
+    want_w, want_b = ctx.needs_input_grad[1], pb is not None and ctx.needs_input_grad[2]
+    tw = _fused_grad_target(pw) if want_w else None
+    tb = _fused_grad_target(pb) if want_b else None
+    fused = (want_w or want_b) and (not want_w or tw is not None) and (not want_b or tb is not None)
+    dx, dw, db = ops.linear_bwd(dlogits, x, w, ctx.needs_input_grad[0], want_w, want_b, tw if fused else None, tb if fused else None)
+    return (dx, None, None) if fused else (dx, dw, db)
+
+
+class _LinearFn(torch.autograd.Function):
+    """logits = x w^T + b (pcgan_linear_softmax_fwd's logits) with pcgan_linear_bwd as its backward"""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        from . import inception as I
+        x, w, b = _c(x), _c(w), _c(b)
+        ctx.params = (w, b)
+        ctx.save_for_backward(x, w)
+        return I.linear_softmax(x, w, b)[0]
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, w = ctx.saved_tensors
+        return _linear_backward(ctx, _c(dlogits), x, w)
+
+
+def linear(x, w, b):
+    """nn.Linear on (N, C) rows, differentiable"""
+    return _LinearFn.apply(x, w, b)
+
+
+class _LinearCeFn(torch.autograd.Function):
+    """nn.Linear + nn.CrossEntropyLoss(weight) as ONE node (pcgan_linear_ce_fwd): the forward launch leaves d loss / d logits behind, the
+    backward is pcgan_linear_bwd.  Only `loss` is differentiable; logits, pred and correct are by-products for the caller's accuracy."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, labels, class_weight):
+        x, w, b = _c(x), _c(w), _c(b)
+        want = x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)
+        loss, logits, dlogits, pred, correct = ops.linear_ce_fwd(x, w, b, _c(labels), class_weight, want)
+        ctx.params = (w, b)
+        ctx.save_for_backward(x, w, dlogits)
+        ctx.mark_non_differentiable(logits, pred, correct)
+        return loss, logits, pred, correct
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        x, w, dlogits = ctx.saved_tensors
+        # d loss / d logits, scaled by the upstream scalar which stays on the device
+        dl = ops.scale(dlogits, _c(dloss).reshape(1))
+        return _linear_backward(ctx, dl, x, w) + (None, None)
+
+
+def linear_cross_entropy(x, w, b, labels, class_weight=None):
+    """(loss, logits, pred, correct) of CrossEntropyLoss(class_weight)(nn.Linear(x), labels), mean reduction; pred = first arg-max of
+    every row, correct = number of rows with pred == label (device tensors)"""
+    return _LinearCeFn.apply(x, w, b, labels, class_weight)
+
+
 def bce_loss(pred, target_n):
     """nn.BCELoss(mean) of pred[N,...] against a per-sample target (float tensor [N])."""
     return _LossFn.apply('bce', pred, target_n)

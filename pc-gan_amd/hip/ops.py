@@ -1291,6 +1291,77 @@ def global_pool_bwd(dy, arg, in_hw, is_max):
     return dx
 
 
+# ---------------------------------------------------------------- classifier head, training pass (csrc/linear_head.hip)
+_CE_WS = {}
+
+
+def _ce_workspace(device, nbytes):
+    """the forward call's workspace, one per (device, stream): its first word is the kernel's arrival ticket, zero before the first call
+    and left zero by every call (include/pcgan_hip.h), so it is allocated zeroed once and grown zeroed"""
+    key = (device, _raw_stream())
+    ws = _CE_WS.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _CE_WS[key] = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def _head_check(what, x, w, b):
+    _chk(x, w, b)
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or (b is not None and tuple(b.shape) != (w.shape[0],)):
+        raise RuntimeError('%s: x %s, w %s, b %s do not form nn.Linear(C -> K) of (N, C) rows'
+                           % (what, tuple(x.shape), tuple(w.shape), None if b is None else tuple(b.shape)))
+    if w.device != x.device or (b is not None and b.device != x.device):
+        raise RuntimeError('%s: x, w and b must be on one device' % what)
+
+
+def linear_ce_fwd(x, w, b, labels, class_weight=None, want_grad=True):
+    """(loss, logits, dlogits, pred, correct) of nn.Linear(C -> K) + CrossEntropyLoss(class_weight) through pcgan_linear_ce_fwd: x (N, C),
+    w (K, C), b (K,) or None, labels (N,) int64, class_weight (K,) or None.  loss is a 0-dim fp32 tensor, pred (N,) int64, correct a
+    0-dim int32 tensor -- all on the device, nothing is read back; dlogits = d loss / d logits (None unless want_grad)."""
+    _head_check('linear_ce_fwd', x, w, b)
+    _chk(class_weight)
+    N, C = x.shape
+    K = w.shape[0]
+    if not labels.is_cuda or labels.dtype != torch.int64 or not labels.is_contiguous() or tuple(labels.shape) != (N,):
+        raise RuntimeError('linear_ce_fwd: labels must be a contiguous int64 GPU tensor of shape (%d,), got %s %s on %s'
+                           % (N, labels.dtype, tuple(labels.shape), labels.device))
+    if class_weight is not None and tuple(class_weight.shape) != (K,):
+        raise RuntimeError('linear_ce_fwd: class_weight of shape %s for %d classes' % (tuple(class_weight.shape), K))
+    lib = _L.load()
+    nbytes = lib.pcgan_linear_ce_workspace_bytes(N)
+    ws = _ce_workspace(x.device, nbytes) if nbytes else None
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    logits = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    pred = torch.empty((N,), dtype=torch.int64, device=x.device)
+    correct = torch.empty((), dtype=torch.int32, device=x.device)
+    _L.check(lib.pcgan_linear_ce_fwd(_p(x), _p(w), _p(b), _p(labels), _p(class_weight), _p(logits), _p(dlogits), _p(loss), _p(pred),
+                                     _p(correct), _p(ws), nbytes, N, C, K, F32, _stream()), 'linear_ce_fwd')
+    return loss, logits, dlogits, pred, correct
+
+
+def linear_bwd(dlogits, x, w, want_dx=True, want_dw=True, want_db=True, dw_into=None, db_into=None):
+    """(dx, dw, db) of logits = x w^T + b through pcgan_linear_bwd.  dw_into / db_into: buffers the weight / bias gradient is ADDED to
+    (a FusedAdam gradient buffer; both or neither, as one accumulate flag covers the launch); the returned dw / db are then those."""
+    _head_check('linear_bwd', x, w, None)
+    _chk(dlogits, dw_into, db_into)
+    N, C = x.shape
+    K = w.shape[0]
+    if tuple(dlogits.shape) != (N, K):
+        raise RuntimeError('linear_bwd: dlogits of shape %s for (%d, %d) logits' % (tuple(dlogits.shape), N, K))
+    acc = dw_into is not None or db_into is not None
+    if acc and ((want_dw and dw_into is None) or (want_db and db_into is None)):
+        raise RuntimeError('linear_bwd: accumulate into both of dw and db or into neither')
+    dx = torch.empty_like(x) if want_dx else None
+    dw = (dw_into if acc else torch.empty_like(w)) if want_dw else None
+    db = (db_into if acc else torch.empty((K,), dtype=torch.float32, device=x.device)) if want_db else None
+    if dw is not None and tuple(dw.shape) != (K, C) or db is not None and tuple(db.shape) != (K,):
+        raise RuntimeError('linear_bwd: gradient buffers do not match w (%d, %d) / b (%d,)' % (K, C, K))
+    _L.check(_L.load().pcgan_linear_bwd(_p(dlogits), _p(x), _p(w), _p(dx), _p(dw), _p(db), N, C, K, int(acc), F32, _stream()),
+             'linear_bwd')
+    return dx, dw, db
+
+
 def bilinear_fwd(x, size):
     dt = _act(x)
     N, C, H, W = x.shape

@@ -514,7 +514,13 @@ class Normalize(tnn.Module):
 class ResNet(tnn.Module):
     """The reference's classifier wrapper (models/networks.py:1258-1285) that classification.py trains and the Inception Score loads
     (compute_inception_score.py:31-36): state_dict keys model.conv1.weight ... model.fc.bias.  forward runs the HIP trunk (eval-mode
-    BatchNorm after .eval()), the global average pool and the classifier head kernel (pcgan_linear_softmax_fwd); forward only.
+    BatchNorm after .eval()), the global average pool and the classifier head kernel (pcgan_linear_softmax_fwd).
+
+    Two paths.  INFERENCE -- gradients off, or no parameter and no input that wants one -- is the forward-only path the Inception Score
+    uses, under no_grad.  TRAINING -- train mode, or gradients enabled and a parameter or the input requiring one -- returns logits with
+    an autograd graph (the reference's `self.model(x)`, models/networks.py:1284-1285): trunk features() with train-mode BatchNorm
+    (running statistics and num_batches_tracked move as in the reference), global average pool, linear head.  `classify(x, labels)` is
+    the training loop's entry (classification.py:376-384): the head and CrossEntropyLoss as one node, (loss, logits, pred, correct).
     resnet101 / resnet152 are outside the HIP path."""
 
     def __init__(self, input_nc=3, num_classes=0, which_model='resnet18', pretrained=False, dropout=0.):
@@ -523,14 +529,46 @@ class ResNet(tnn.Module):
         table = {'resnet18': resnet.resnet18, 'resnet34': resnet.resnet34, 'resnet50': resnet.resnet50}
         if which_model not in table:
             raise NotImplementedError('pcgan_amd: classifier [%s] is outside the HIP path (resnet18, resnet34, resnet50)' % which_model)
-        self.model = table[which_model](pretrained, num_classes=num_classes, dropout=dropout)
+        # as the reference builds it (:1262-1282): the 1000-class net first, then a new fc -- both draw from torch's generator, so a
+        # seeded construction + classification.py's weights_init gives the reference's initial weights
+        model = table[which_model](pretrained, dropout=dropout)
+        model.fc = tnn.Linear(model.fc.in_features, num_classes)
+        self.model = model
 
     def forward(self, x, probs=False):
-        """logits (N, num_classes); with probs=True (logits, softmax probabilities)"""
+        """logits (N, num_classes); with probs=True (logits, softmax probabilities), always on the inference path"""
         from ..hip import inception as I
-        if x.requires_grad:
-            raise RuntimeError('networks.ResNet (HIP) is forward-only: the input requires grad and the head has no backward pass')
+        if not probs and self._wants_graph(x):      # probs=True asks for the scorer's by-product: always the inference path
+            fc = self.model.fc
+            return HF.linear(self._pooled(x), fc.weight, fc.bias)
         with torch.no_grad():
             pooled = I.global_avg_pool(self.model.features(x)).flatten(1)
             logits, p = I.linear_softmax(pooled, self.model.fc.weight, self.model.fc.bias)
         return (logits, p) if probs else logits
+
+    def _wants_graph(self, x):
+        if not torch.is_grad_enabled():
+            return False
+        return self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    def _pooled(self, x):
+        """(N, feature_dim) fp32 rows of the trunk's globally averaged features, differentiable"""
+        return HF.cast(HF.global_pool(self.model.features(x), False), torch.float32).flatten(1)
+
+    def classify(self, x, labels, class_weight=None):
+        """(loss, logits, pred, correct) of one batch: CrossEntropyLoss(weight=class_weight)(self(x), labels) with its default mean
+        reduction, the logits, the first arg-max of every row (the reference's get_prediction) and the number of rows it gets right
+        (device tensors: nothing is read back).  Only `loss` carries the graph.  labels: (N,) int64 on x's device."""
+        fc = self.model.fc
+        pooled = self._pooled(x) if torch.is_grad_enabled() else self._pooled(x).detach()
+        return HF.linear_cross_entropy(pooled, fc.weight, fc.bias, labels, class_weight)
+
+    def load_pretrained(self, state_dict):
+        """reference models/networks.py:1301-1307: the trunk of an (ImageNet) checkpoint of the bare net -- keys conv1.weight ... without
+        the `model.` prefix; `fc*` is dropped (another class count), the rest loads non-strictly into self.model"""
+        if isinstance(state_dict, str):
+            state_dict = torch.load(state_dict, map_location='cpu')
+        state_dict = {k: v for k, v in state_dict.items() if not k.startswith('fc')}
+        self.model.load_state_dict(state_dict, strict=False)
+        from ..hip import ops
+        ops.invalidate_packed_weights()
