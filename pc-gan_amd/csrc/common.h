@@ -77,6 +77,11 @@ static inline int ilog2_exact(int v) {
     return ((1 << l) == v) ? l : -1;
 }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// workgroups of a grid-stride kernel: ceil(total / per_block), at least 1, at most `cap`
+static inline unsigned capped_blocks(size_t total, unsigned per_block, unsigned cap) {
+    const size_t b = (total + per_block - 1) / per_block;
+    return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
+}
 
 __device__ __forceinline__ float act_apply(float v, int act, float slope) {
     switch (act) {

@@ -19,7 +19,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // TA = bf16 (the bf16 path, desc.dtype = PCGAN_BF16): the stored bf16 activations go to LDS as they are, the fp32 weights are rounded
 // to bf16 on their way there, ONE v_mfma_f32_32x32x16_bf16 per block and stage, no scaling -- plain mixed precision as in the
-// one-product form of the residual-convolution kernels (bf16x6_conv.hip).
+// one-product form of the residual-convolution kernels (halo_conv.hip, hsplit_wgrad.hip).
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 

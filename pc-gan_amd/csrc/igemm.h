@@ -273,12 +273,6 @@ static inline size_t esz(const pcgan_conv_desc* d) { return d->dtype == PCGAN_BF
         else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, float>), GRID, dim3(256), 0, st, ARG);                      \
     } while (0)
 
-// workgroups of a grid-stride kernel: ceil(total / per_block), at least 1, at most `cap`
-static inline unsigned capped_blocks(size_t total, unsigned per_block, unsigned cap) {
-    const size_t b = (total + per_block - 1) / per_block;
-    return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
-}
-
 // ---- the host unit (igemm_conv.hip) for the kernel units ---------------------------------------------------------------------
 // record of the last launch launch_igemm decided (pcgan_igemm_last_launch)
 void record_launch(int form, int mode, int bm, int bp, int ks, int nphase);

@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(1024) instnorm_fwd_fused_kernel(const T* __res
         m2_nc[plane] = m2;
     }
     // largest magnitude of y over this plane: the fp16 route of the convolution that reads y scales by the largest of them
-    // (bf16x6_conv.hip; a plain store per plane -- one atomic maximum for the tensor serialises 8192 workgroups on one address)
+    // (amax.hip; a plain store per plane -- one atomic maximum for the tensor serialises 8192 workgroups on one address)
     if (y_pmax) {
         am = block_max(am, scratch);
         if (threadIdx.x == 0) y_pmax[plane] = am;

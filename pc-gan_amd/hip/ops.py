@@ -320,7 +320,7 @@ def _weight_stamp(w):
 
 
 # The residual-block convolutions (forward, data gradient, weight gradient) run on the bf16 matrix pipe with every fp32
-# operand split exactly into three bf16 pieces, six piece products per term (csrc/bf16x6_conv.hip): fp32-level error at
+# operand split exactly into three bf16 pieces, six piece products per term (csrc/bsplit_conv.hip, csrc/halo_conv.hip): fp32-level error at
 # 1.5x the speed of the fp32 MFMA kernels.  PCGAN_BF16X6=0 routes them back to the fp32 MFMA implicit GEMM (A/B runs).
 BF16X6 = os.environ.get('PCGAN_BF16X6', '1') == '1'
 BSPLIT_MIN_PIXELS = 16384    # output pixels (N*P*Q) from which the one-tile-shape split kernels fill the chip (tests lower it)
@@ -333,7 +333,7 @@ PASS_BWD_HGEMM = 105
 PASS_FWD_THIN = 106      # pcgan_conv2d_thin_pack: <= 4 gathered channels (7x7 stems, first PatchGAN layer; data gradient of the 64 -> 3 head)
 PASS_BWD_THIN = 107
 # Which split the fp32 residual convolutions (forward, data gradient) take on the matrix pipe: 'f16' = two scaled fp16 pieces, three
-# products (csrc/bf16x6_conv.hip, "fp16 route"); 'bf16' = three bf16 pieces, six products.  Same measured error, half the MFMAs.
+# products (csrc/halo_conv.hip PK_F16X2, csrc/hsplit_wgrad.hip: the "fp16 route"); 'bf16' = three bf16 pieces, six products.  Same measured error, half the MFMAs.
 HSPLIT = os.environ.get('PCGAN_SPLIT', 'f16') == 'f16'
 # ... and whether every other convolution with a multiple of 16 gathered channels runs the fp16 two-piece form of the packed
 # implicit GEMM (csrc/hgemm.hip hgemm_kernel) instead of the fp32 MFMA one

@@ -1,4 +1,5 @@
-"""GPU: the opt-in bf16-split convolution forward (csrc/bf16x6_conv.hip, through the C-ABI) against the oracle's convolution
+"""GPU: the opt-in bf16-split convolution forward (kernels csrc/bsplit_conv.hip and csrc/halo_conv.hip, host side
+csrc/bf16x6_conv.hip, through the C-ABI) against the oracle's convolution
 in float64: its error must be at the level of the fp32 path's own (tolerance 3e-6 relative L2, the fp32 MFMA kernel measures
 ~6e-7 at K = 2304), for reflect and zero padding, ragged pixel / channel tiles, 1x1 / 3x3 / 5x5 filters, bias + activation."""
 import ctypes
@@ -158,7 +159,7 @@ def test_bsplit_weight_gradient(dev, N, C, H, W, K, acc):
     assert e(got) < 3e-6 and e(got) < 4 * e(dw32.double().cpu()) + 5e-7, (e(got), e(dw32.double().cpu()))
 
 
-# ---- the fp16 two-piece route (csrc/bf16x6_conv.hip "fp16 route"; C-ABI pcgan_conv2d_*_hsplit) ------------------------------------
+# ---- the fp16 two-piece route (csrc/halo_conv.hip PK_F16X2, csrc/hsplit_wgrad.hip; C-ABI pcgan_conv2d_*_hsplit) ------------------------------------
 def _hsplit(dev, N, C, H, W, K, x, w, dgrad):
     """forward (x = input) or data gradient (x = dy) through the fp16 route, and through the fp32 kernels of the product"""
     from pcgan_amd.hip import lib as L, ops
