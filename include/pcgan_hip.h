@@ -564,6 +564,41 @@ int pcgan_linear_ce_fwd(const void* x, const float* w, const float* b, const int
 int pcgan_linear_bwd(const void* dlogits, const void* x, const float* w, void* dx, float* dw, float* db, int N, int C, int K,
                      int accumulate, int dtype, pcgan_stream_t s);
 
+/* ---- head of the projection discriminator (csrc/proj_head.hip) -------------------------------------------------------------------------
+ * NLayerProjectionDiscriminator.forward with proj=True ("cGANs with Projection Discriminator").  Replaces
+ *   h = torch.sum(self.phi(input), dim=(2, 3), keepdim=True)                 models/networks.py:830
+ *   w_y = self.l_y(y)                                                        models/networks.py:831   (l_y = Conv2d(nz, C, 1))
+ *   output = torch.sum(h * w_y, dim=1, keepdim=True) + self.psi(h)           models/networks.py:832   (psi = Conv2d(C, 1, 1, padding=1))
+ *   torch.sigmoid(output) if self._sigm                                      models/networks.py:838
+ * and autograd's backward through them.  p[B][C][HW] is the trunk's output (dtype: PCGAN_F32 or PCGAN_BF16, NCHW contiguous, any
+ * element-aligned address), y[By][nz] fp32 with By = 1 (broadcast over the batch) or B, psi_w[C], psi_b[1], ly_w[C][nz], ly_b[C] fp32.
+ *   h[b][c]      = sum of the plane p[b][c]                                   (fp32, kept for the backward pass)
+ *   wy[b][c]     = sum_j ly_w[c][j] y[b][j] + ly_b[c]
+ *   out[b][0][i][j] = sum_c h[b][c] wy[b][c] + psi_b + [i == j == 1] sum_c psi_w[c] h[b][c]       [B][1][3][3], in p's dtype
+ * sigmoid != 0 applies 1 / (1 + exp(-x)) to out.  Sizes: B, C, HW >= 1 (HW <= 2^27, B * C < 2^31), 1 <= nz <= 16.
+ *
+ * pcgan_proj_head_bwd: g[B][1][3][3] (p's dtype) is d loss / d out; with sigmoid != 0 it is first multiplied by o (1 - o) of the output
+ * recomputed in float64 from h.  With G[b] = sum_ij g[b][i][j] and gc[b] = g[b][1][1]:
+ *   dp[b][c][:]  = G[b] wy[b][c] + gc[b] psi_w[c]            (p's dtype, always overwritten)
+ *   dpsi_w[c]   (+)= sum_b gc[b] h[b][c]         dpsi_b (+)= sum_b G[b]
+ *   dly_w[c][j] (+)= sum_b G[b] h[b][c] y[b][j]   dly_b[c] (+)= sum_b G[b] h[b][c]
+ *   dy[b][j]     = sum_c G[b] h[b][c] ly_w[c][j]             (summed over b as well when By = 1; always overwritten)
+ * Every output may be NULL (not wanted), not all of them.  accumulate != 0 adds the four parameter gradients to what their buffers hold
+ * (a FusedAdam gradient buffer: D runs several times per step), else overwrites them.
+ * workspace: pcgan_proj_head_bwd_workspace_bytes(B, nz) bytes (0: sizes out of range), 8-byte aligned, caller-owned, no state kept in
+ * it between calls.
+ *
+ * Every sum runs in a fixed order in float64 and is rounded once; no float atomics: results are bit-identical from run to run and beside
+ * other streams' work.  Two launches per direction.  p / dp that are 16-byte aligned are accessed 128 bits at a time, otherwise element
+ * by element -- the same values either way (planes start element-aligned only when HW is no multiple of 4: 7x7, 15x15, 31x31 maps). */
+int pcgan_proj_head_fwd(const void* p, const float* y, const float* psi_w, const float* psi_b, const float* ly_w, const float* ly_b,
+                        void* out, float* h, int B, int C, int HW, int nz, int By, int sigmoid, int dtype, pcgan_stream_t s);
+size_t pcgan_proj_head_bwd_workspace_bytes(int B, int nz);
+int pcgan_proj_head_bwd(const void* g, const float* h, const float* y, const float* psi_w, const float* psi_b, const float* ly_w,
+                        const float* ly_b, void* dp, float* dpsi_w, float* dpsi_b, float* dly_w, float* dly_b, float* dy, void* workspace,
+                        size_t workspace_bytes, int B, int C, int HW, int nz, int By, int sigmoid, int accumulate, int dtype,
+                        pcgan_stream_t s);
+
 /* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),

@@ -646,6 +646,42 @@ def linear_cross_entropy(x, w, b, labels, class_weight=None):
     return _LinearCeFn.apply(x, w, b, labels, class_weight)
 
 
+# ---------------------------------------------------------------------------- projection discriminator head
+class _ProjectionHeadFn(torch.autograd.Function):
+    """The head of NLayerProjectionDiscriminator (reference models/networks.py:830-838) as ONE node: pcgan_proj_head_fwd leaves the plane
+    sums h behind, the backward is pcgan_proj_head_bwd.  The four parameter gradients go straight into the FusedAdam gradient buffer when
+    every wanted one has a slice there (autograd then receives None for them, as in _Conv2dFn.backward)."""
+
+    @staticmethod
+    def forward(ctx, p, y, psi_w, psi_b, ly_w, ly_b, sigmoid):
+        p, y = _c(p), _c(y)
+        out, h = ops.proj_head_fwd(p, y, _c(psi_w), _c(psi_b), _c(ly_w), _c(ly_b), sigmoid)
+        ctx.cfg = (tuple(p.shape[2:]), bool(sigmoid))
+        ctx.params = (psi_w, psi_b, ly_w, ly_b)
+        ctx.save_for_backward(h, y, psi_w, psi_b, ly_w, ly_b)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        h, y, psi_w, psi_b, ly_w, ly_b = ctx.saved_tensors
+        hw, sigmoid = ctx.cfg
+        want = tuple(ctx.needs_input_grad[2:6])
+        targets = [_fused_grad_target(q) if w else None for q, w in zip(ctx.params, want)]
+        fused = any(want) and all(t is not None for t, w in zip(targets, want) if w)
+        res = ops.proj_head_bwd(_c(g), h, y, _c(psi_w), _c(psi_b), _c(ly_w), _c(ly_b), hw, sigmoid, ctx.needs_input_grad[0], want,
+                                ctx.needs_input_grad[1], targets if fused else None)
+        dp, dy = res[0], res[5]
+        if fused:
+            return dp, dy, None, None, None, None, None
+        return (dp, dy) + tuple(None if t is None else t.view_as(q) for t, q in zip(res[1:5], ctx.params)) + (None,)
+
+
+def projection_head(p, y, psi_w, psi_b, ly_w, ly_b, sigmoid):
+    """out (B, 1, 3, 3) = sum_c h wy + psi(h) of the projection discriminator, h = plane sums of p (B, C, H, W), wy = l_y(y); y is
+    (By, nz) fp32 with By in {1, B}; sigmoid folds torch.sigmoid in.  Gradients reach p, y and the four parameters."""
+    return _ProjectionHeadFn.apply(p, y, psi_w, psi_b, ly_w, ly_b, sigmoid)
+
+
 def bce_loss(pred, target_n):
     """nn.BCELoss(mean) of pred[N,...] against a per-sample target (float tensor [N])."""
     return _LossFn.apply('bce', pred, target_n)

@@ -162,6 +162,9 @@ SIGNATURES = {
     'pcgan_linear_ce_workspace_bytes': (_sz, [_i]),
     'pcgan_linear_ce_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     'pcgan_linear_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'pcgan_proj_head_fwd': (_i, [_vp] * 8 + [_i] * 7 + [_vp]),
+    'pcgan_proj_head_bwd_workspace_bytes': (_sz, [_i, _i]),
+    'pcgan_proj_head_bwd': (_i, [_vp] * 14 + [_sz] + [_i] * 8 + [_vp]),
 }
 
 _lib = None

@@ -1362,6 +1362,83 @@ def linear_bwd(dlogits, x, w, want_dx=True, want_dw=True, want_db=True, dw_into=
     return dx, dw, db
 
 
+# ---------------------------------------------------------------- projection discriminator head (csrc/proj_head.hip)
+def _proj_check(what, B, C, y, psi_w, psi_b, ly_w, ly_b):
+    _chk(y, psi_w, psi_b, ly_w, ly_b)
+    if y.dim() != 2:
+        raise RuntimeError('%s: y must be (By, nz), got %s' % (what, tuple(y.shape)))
+    By, nz = y.shape
+    if psi_w.numel() != C or psi_b.numel() != 1 or ly_w.numel() != C * nz or ly_b.numel() != C or (ly_w.dim() > 1 and ly_w.shape[0] != C):
+        raise RuntimeError('%s: psi.weight %s, psi.bias %s, l_y.weight %s, l_y.bias %s do not form the head of %d channels and nz = %d'
+                           % (what, tuple(psi_w.shape), tuple(psi_b.shape), tuple(ly_w.shape), tuple(ly_b.shape), C, nz))
+    return By, nz
+
+
+_PROJ_WS = {}
+
+
+def _proj_workspace(device, nbytes):
+    """the backward call's workspace, one per (device, stream), grown on demand: it carries values from the call's first launch to its
+    second and no state between calls, so calls in stream order share it"""
+    key = (device, _raw_stream())
+    ws = _PROJ_WS.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _PROJ_WS[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def proj_head_fwd(p, y, psi_w, psi_b, ly_w, ly_b, sigmoid):
+    """(out, h) of the projection discriminator's head through pcgan_proj_head_fwd: p (B, C, H, W) fp32 or bf16, y (By, nz) fp32 with
+    By in {1, B}, psi.weight (1, C, 1, 1), psi.bias (1,), l_y.weight (C, nz, 1, 1), l_y.bias (C,).  out is (B, 1, 3, 3) in p's storage
+    type, h (B, C) fp32 the plane sums the backward pass needs."""
+    dt = _act(p)
+    if p.dim() != 4:
+        raise RuntimeError('proj_head_fwd: p must be (B, C, H, W), got %s' % (tuple(p.shape),))
+    B, C, H, W = p.shape
+    By, nz = _proj_check('proj_head_fwd', B, C, y, psi_w, psi_b, ly_w, ly_b)
+    out = torch.empty((B, 1, 3, 3), dtype=p.dtype, device=p.device)
+    h = torch.empty((B, C), dtype=torch.float32, device=p.device)
+    _L.check(_L.load().pcgan_proj_head_fwd(_p(p), _p(y), _p(psi_w), _p(psi_b), _p(ly_w), _p(ly_b), _p(out), _p(h), B, C, H * W, nz, By,
+                                           int(bool(sigmoid)), dt, _stream()), 'proj_head_fwd')
+    return out, h
+
+
+def proj_head_bwd(g, h, y, psi_w, psi_b, ly_w, ly_b, in_hw, sigmoid, want_dp=True, want_params=(True, True, True, True), want_dy=True,
+                  into=None):
+    """(dp, dpsi_w, dpsi_b, dly_w, dly_b, dy) through pcgan_proj_head_bwd; g (B, 1, 3, 3) in the storage type dp gets.  want_params: which
+    of the four parameter gradients to compute.  into: four buffers (None where not wanted) the wanted parameter gradients are ADDED to
+    (FusedAdam gradient buffers; one accumulate flag covers the launch); the returned gradients are then those."""
+    dt = _act(g)
+    _chk(h)
+    B, C = h.shape
+    By, nz = _proj_check('proj_head_bwd', B, C, y, psi_w, psi_b, ly_w, ly_b)
+    if tuple(g.shape) != (B, 1, 3, 3):
+        raise RuntimeError('proj_head_bwd: g of shape %s for a (%d, 1, 3, 3) output' % (tuple(g.shape), B))
+    H, W = in_hw
+    acc = into is not None
+    grads = []
+    for i, like in enumerate((psi_w, psi_b, ly_w, ly_b)):
+        if not want_params[i]:
+            grads.append(None)
+        elif acc:
+            t = into[i]
+            if t is None or t.numel() != like.numel():
+                raise RuntimeError('proj_head_bwd: gradient buffer %d does not match its parameter' % i)
+            _chk(t)
+            grads.append(t)
+        else:
+            grads.append(torch.empty_like(like))
+    dp = torch.empty((B, C, H, W), dtype=g.dtype, device=g.device) if want_dp else None
+    dy = torch.empty((By, nz), dtype=torch.float32, device=g.device) if want_dy else None
+    lib = _L.load()
+    nbytes = lib.pcgan_proj_head_bwd_workspace_bytes(B, nz)
+    ws = _proj_workspace(g.device, nbytes)
+    _L.check(lib.pcgan_proj_head_bwd(_p(g), _p(h), _p(y), _p(psi_w), _p(psi_b), _p(ly_w), _p(ly_b), _p(dp), _p(grads[0]), _p(grads[1]),
+                                     _p(grads[2]), _p(grads[3]), _p(dy), _p(ws), nbytes, B, C, H * W, nz, By, int(bool(sigmoid)), int(acc),
+                                     dt, _stream()), 'proj_head_bwd')
+    return (dp,) + tuple(grads) + (dy,)
+
+
 def bilinear_fwd(x, size):
     dt = _act(x)
     N, C, H, W = x.shape

@@ -132,7 +132,10 @@ def define_D(input_nc, nz, ndf, which_model_netD, n_layers_D=3, norm='batch', us
         netD = NLayerDiscriminator(input_nc, nz, ndf, n_layers=3, norm_layer=norm_layer, use_sigmoid=use_sigmoid)
     elif which_model_netD == 'n_layers':
         netD = NLayerDiscriminator(input_nc, nz, ndf, n_layers_D, norm_layer=norm_layer, use_sigmoid=use_sigmoid)
-    elif which_model_netD in ('n_layers_multi', 'n_layers_proj', 'pixel', 'pyramid', 'gan_stability',
+    elif which_model_netD == 'n_layers_proj':
+        netD = NLayerProjectionDiscriminator(input_nc, nz, ndf, n_layers_D, norm_layer=norm_layer, use_sigmoid=use_sigmoid,
+                                             proj=use_projection)
+    elif which_model_netD in ('n_layers_multi', 'pixel', 'pyramid', 'gan_stability',
                               'gan_stability_class', 'mnist_fc'):
         raise NotImplementedError('Discriminator [%s] is outside the MI355X hot path (SURVEY.md section 8); '
                                   'use basic / n_layers' % which_model_netD)
@@ -323,6 +326,51 @@ class NLayerDiscriminator(tnn.Module):
     def forward(self, input, z=None):
         x = HF.concat_z(input, z) if z is not None else input
         return run_sequential(self.model, x)
+
+
+class HeadConv2d(tnn.Conv2d):
+    """The parameters of a 1x1 convolution of the projection head -- the reference's key names, shapes, constructor draws and (by its
+    class name) init_weights rule -- whose arithmetic lives in the head kernel (HF.projection_head): it is never called as a layer."""
+
+    def forward(self, x):
+        raise RuntimeError('pcgan_amd: HeadConv2d only holds parameters; the projection head kernel computes with them')
+
+
+class NLayerProjectionDiscriminator(tnn.Module):
+    """reference models/networks.py:787-838 with proj=True ("cGANs with Projection Discriminator"): phi = NLayerDiscriminator's trunk
+    without its last convolution, applied to the image alone; out[B,1,3,3] = sum_c h wy + psi(h) with h the plane SUMS of phi's output,
+    wy = l_y(y), psi a 1x1 convolution with padding 1 (so only the centre cell sees h).  state_dict keys phi.*, psi.*, l_y.*."""
+
+    def __init__(self, input_nc, nz, ndf=64, n_layers=3, norm_layer=hnn.BatchNorm2d, use_sigmoid=False, proj=True):
+        super().__init__()
+        if not proj:
+            raise NotImplementedError('NLayerProjectionDiscriminator with use_projection=False (proj=False) is outside the MI355X hot '
+                                      'path; use n_layers for the concatenated rating')
+        if nz < 1:
+            raise NotImplementedError('Discriminator [n_layers_proj] projects a rating (nz >= 1): the unconditional discriminator of '
+                                      'wsgan_cycle (nz = %d) cannot be one; use basic / n_layers there' % nz)
+        self._proj, self._sigm, self.nz = proj, use_sigmoid, nz
+        use_bias = _is_instance_norm(norm_layer)
+        seq = [hnn.Conv2d(input_nc, ndf, kernel_size=4, stride=2, padding=1), tnn.LeakyReLU(0.2, True)]
+        mult = 1
+        for n in range(1, n_layers):
+            prev, mult = mult, min(2 ** n, 8)
+            seq += [hnn.Conv2d(ndf * prev, ndf * mult, kernel_size=4, stride=2, padding=1, bias=use_bias),
+                    norm_layer(ndf * mult), tnn.LeakyReLU(0.2, True)]
+        prev, mult = mult, min(2 ** n_layers, 8)
+        seq += [hnn.Conv2d(ndf * prev, ndf * mult, kernel_size=4, stride=1, padding=1, bias=use_bias),
+                norm_layer(ndf * mult), tnn.LeakyReLU(0.2, True)]
+        self.phi = tnn.Sequential(*seq)
+        self.psi = HeadConv2d(ndf * mult, 1, kernel_size=1, stride=1, padding=1)
+        self.l_y = HeadConv2d(nz, ndf * mult, kernel_size=1, stride=1)
+
+    def forward(self, input, y=None):
+        if y is None:
+            raise RuntimeError('pcgan_amd: the projection discriminator needs the rating y')
+        p = run_sequential(self.phi, input)
+        if y.numel() not in (self.nz, p.shape[0] * self.nz):
+            raise RuntimeError('pcgan_amd: y of shape %s for batch %d and nz = %d' % (tuple(y.shape), p.shape[0], self.nz))
+        return HF.projection_head(p, y.reshape(-1, self.nz), self.psi.weight, self.psi.bias, self.l_y.weight, self.l_y.bias, self._sigm)
 
 
 # ------------------------------------------------------------------------- encoders
