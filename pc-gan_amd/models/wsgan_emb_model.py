@@ -12,8 +12,10 @@ pcgan_amd.hip.  What is different by design:
   * `--lr_E > 0` (update_G_and_E): the reference's own branch fails on torch >= 1.5 with an in-place-modification error
     (SURVEY.md D13); here it runs with the semantics of the PyTorch it was written for -- the optimizers step without telling
     autograd, and the second backward pass through the RETAINED graph reads the updated weights where a backward formula reads
-    a weight and the old forward pass's saved activations elsewhere (oracle/step_ref.py: AdamThroughData; parity unpinned, the
-    semantics are DEFINED there).  FusedAdam updates the flat buffer through raw pointers, which is exactly that.
+    a weight and the old forward pass's saved activations elsewhere (oracle/step_ref.py: AdamThroughData DEFINES the optimizer's
+    semantics; the branch's algorithm is pinned against the reference's own run of it by the golden step test,
+    tests/test_oracle_golden.py::test_lr_E_step_matches_the_reference_run_with_the_defined_optimizer).  FusedAdam updates the flat
+    buffer through raw pointers, which is exactly that.
 """
 import os
 from collections import OrderedDict

@@ -57,7 +57,7 @@ def _run(dev, N, C, H, W, K, k, pad, pad_mode, act=0, bias=True, seed=0):
 ])
 def test_bsplit_forward_has_fp32_accuracy(dev, N, C, H, W, K, k, pad, mode, act):
     e6, e32 = _run(dev, N, C, H, W, K, k, pad, mode, act)
-    assert e6 < 3e-6 and e6 < 4 * e32 + 5e-7, (e6, e32)
+    assert e6 < 3e-6 and e6 < 2 * e32 + 5e-7, (e6, e32)
 
 
 def test_bsplit_unsupported_shapes_are_refused(dev):
@@ -124,7 +124,7 @@ def test_bsplit_reflect_data_gradient(dev, N, C, H, W, K):
     dx32 = ops.conv2d_bwd_data(dyd, wd, (H, W), 1, 1, 1)
     torch.cuda.synchronize()
     e = lambda t: float((t.double().cpu() - ref).norm() / ref.norm())
-    assert e(dx) < 3e-6 and e(dx) < 4 * e(dx32) + 5e-7, (e(dx), e(dx32))
+    assert e(dx) < 3e-6 and e(dx) < 2 * e(dx32) + 5e-7, (e(dx), e(dx32))
 
 
 @pytest.mark.parametrize('N,C,H,W,K,acc', [
@@ -156,7 +156,7 @@ def test_bsplit_weight_gradient(dev, N, C, H, W, K, acc):
     torch.cuda.synchronize()
     got = dw.double().cpu() - (base.double() if acc else 0)
     e = lambda t: float((t - ref).norm() / ref.norm())
-    assert e(got) < 3e-6 and e(got) < 4 * e(dw32.double().cpu()) + 5e-7, (e(got), e(dw32.double().cpu()))
+    assert e(got) < 3e-6 and e(got) < 2 * e(dw32.double().cpu()) + 5e-7, (e(got), e(dw32.double().cpu()))
 
 
 # ---- the fp16 two-piece route (csrc/halo_conv.hip PK_F16X2, csrc/hsplit_wgrad.hip; C-ABI pcgan_conv2d_*_hsplit) ------------------------------------
@@ -216,7 +216,7 @@ def test_hsplit_forward_has_fp32_accuracy(dev, N, C, H, W, K, data):
     y, y32 = _hsplit(dev, N, C, H, W, K, x, w, False)
     ref = R.conv2d(x.double(), w.double(), None, 1, 1, 1)
     e = lambda t: float((t.double() - ref).norm() / ref.norm())
-    assert e(y) < 3e-6 and e(y) < 4 * e(y32) + 5e-7, (e(y), e(y32))
+    assert e(y) < 3e-6 and e(y) < 2 * e(y32) + 5e-7, (e(y), e(y32))
 
 
 @pytest.mark.parametrize('N,K,H,W,C', HSPLIT_SHAPES)
@@ -232,7 +232,7 @@ def test_hsplit_reflect_data_gradient(dev, N, K, H, W, C, data):
     ref = x.grad
     dx, dx32 = _hsplit(dev, N, C, H, W, K, dy, w, True)
     e = lambda t: float((t.double() - ref).norm() / ref.norm())
-    assert e(dx) < 3e-6 and e(dx) < 4 * e(dx32) + 5e-7, (e(dx), e(dx32))
+    assert e(dx) < 3e-6 and e(dx) < 2 * e(dx32) + 5e-7, (e(dx), e(dx32))
 
 
 def test_absmax_unaligned_and_ragged(dev):
@@ -255,7 +255,7 @@ def test_absmax_unaligned_and_ragged(dev):
     (1, 16, 4, 16, False),       # smallest grid
     (2, 64, 8, 64, True),        # width 64
 ])
-@pytest.mark.parametrize('data', ['normal', 'wide_range'])
+@pytest.mark.parametrize('data', ['normal', 'wide_range', 'tiny', 'huge'])
 def test_hsplit_weight_gradient(dev, N, C, H, W, acc, data):
     """dW of ReflectionPad2d(1) + Conv2d(3x3, 256 output channels) on the fp16 route against autograd in float64 and the fp32 kernel"""
     from pcgan_amd.hip import lib as L, ops
@@ -266,6 +266,10 @@ def test_hsplit_weight_gradient(dev, N, C, H, W, acc, data):
     if data == 'wide_range':
         x = x * torch.pow(10.0, torch.rand(N, C, H, W, generator=g) * 8 - 6)
         dy = dy * torch.pow(10.0, torch.rand(N, K, H, W, generator=g) * 12 - 14)
+    elif data == 'tiny':             # x scaled at the exponent clamp of pow2_scale (the factors of tests/test_gpu_wgrad_rowring.py)
+        x, dy = x * 1e-30, dy * 1e-4
+    elif data == 'huge':
+        x, dy = x * 1e12, dy * 1e8
     w = torch.zeros(K, C, 3, 3, dtype=torch.float64, requires_grad=True)
     R.conv2d(x.double(), w, None, 1, 1, 1).backward(dy.double())
     ref = w.grad
@@ -290,7 +294,7 @@ def test_hsplit_weight_gradient(dev, N, C, H, W, acc, data):
     torch.cuda.synchronize()
     got = dw.double().cpu() - (base.double() if acc else 0.0)
     e = lambda t: float((t - ref).norm() / ref.norm())
-    assert e(got) < (3e-6 if not acc else 1e-5) and (acc or e(got) < 4 * e(dw32.double().cpu()) + 5e-7), (e(got), e(dw32.double().cpu()))
+    assert e(got) < (3e-6 if not acc else 1e-5) and (acc or e(got) < 2 * e(dw32.double().cpu()) + 5e-7), (e(got), e(dw32.double().cpu()))
 
 
 @pytest.mark.parametrize('N,C,H,W,K,k,stride,pad,mode', [
@@ -400,7 +404,7 @@ def test_hsplit_weight_gradient_inline_zero_padding(dev, N, C, H, W, K, k, strid
         ops.HSPLIT = old
     torch.cuda.synchronize()
     e = lambda t: float((t.double().cpu() - ref).norm() / ref.norm())
-    assert e(dw) < 3e-6 and e(dw) < 4 * e(dw32) + 5e-7, (e(dw), e(dw32))
+    assert e(dw) < 3e-6 and e(dw) < 2 * e(dw32) + 5e-7, (e(dw), e(dw32))
     # every tap separately (a wrong border column or row shows in the border taps only)
     per_tap = ((dw.double().cpu() - ref) ** 2).sum(dim=(0, 1)).sqrt() / (ref ** 2).sum(dim=(0, 1)).sqrt()
     assert float(per_tap.max()) < 1e-5, per_tap

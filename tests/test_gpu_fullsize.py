@@ -99,12 +99,20 @@ def test_fullsize_conv_properties(case, dev):
 
 
 def test_fullsize_production_routes_are_the_ones_under_test(dev):
-    """the bs-32 residual weight gradient above runs hsplit_wgrad_kernel (the launch bench.py times), not a fallback"""
+    """the bs-32 residual convolutions above run the kernels bench.py times, not a fallback: the host routes all three passes to the
+    fp16 route ('hsplit'), and below the C-ABI pcgan_conv2d_bwd_weight_hsplit hands the weight gradient to the row-ring form
+    (rowring_wgrad_kernel / rowring_wgrad_bf16_kernel + wgd_reduce_kernel, csrc/wgrad_rowring.hip) -- the host's route name cannot show
+    that choice, so the library option and the form's own shape test are asserted too, for fp32 and bf16 tensors"""
+    import ctypes
     from pcgan_amd.hip import ops
     L = ops._L
     assert ops._plan(L.PASS_BWD_WEIGHT, 32, 256, 32, 32, 256, 3, 3, 1, 1, 1, ops.F32).route == 'hsplit'
     assert ops._plan(L.PASS_FWD, 32, 256, 32, 32, 256, 3, 3, 1, 1, 1, ops.F32).route == 'hsplit'
     assert ops._plan(L.PASS_BWD_DATA, 32, 256, 32, 32, 256, 3, 3, 1, 1, 1, ops.F32).route == 'hsplit'
+    assert L.get_option('wgrad_rowring') == 1
+    for dt in (ops.F32, ops.BF16):
+        d = ops.make_desc(32, 256, 32, 32, 256, 3, 3, 1, 1, 1, dt)
+        assert L.load().pcgan_conv2d_wgrad_rowring_supported(ctypes.byref(d)), dt
 
 
 @pytest.mark.parametrize('route', ['as_routed', 'split_kernels', 'split_kernels_bf16x6', 'fp32_mfma'])

@@ -1,7 +1,7 @@
 """GPU: the convolutions that gather <= 4 channels on the f16 matrix pipe (csrc/thin_conv.hip, through the C-ABI: the 7x7 stems of
 the generator and of the Elo encoder, the first PatchGAN layer, the data gradient of the generator's 64 -> 3 head) against the
 oracle's convolution in float64.  Same bar as the other fp16-route kernels (tests/test_gpu_bf16x6.py): relative L2 <= 3e-6 and within
-4 x the fp32-MFMA kernel's own error on the same data, per output channel when the filter rows span 2^+-20."""
+2 x the fp32-MFMA kernel's own error on the same data + 5e-7; 3e-6 per output channel when the filter rows span 2^+-20."""
 import pytest
 import torch
 
@@ -82,7 +82,7 @@ def test_thin_route_has_fp32_accuracy(dev, monkeypatch, case):
     e16 = float((out - ref).norm() / ref.norm())
     monkeypatch.setattr(ops, 'THIN', False)                               # igemm2_kernel<.., 4> / the generic kernels on fp32 MFMA
     e32 = float((_run(dev, case, src, w, b) - ref).norm() / ref.norm())
-    assert e16 <= 4 * e32 + 5e-7 and e16 < 3e-6, '%s: %.3e (fp32 MFMA route %.3e)' % (case[0], e16, e32)
+    assert e16 <= 2 * e32 + 5e-7 and e16 < 3e-6, '%s: %.3e (fp32 MFMA route %.3e)' % (case[0], e16, e32)
     # every element, not only the norm: a wrong border / ragged-tile pixel must not hide in the L2
     assert float((out - ref).abs().max()) <= 2e-5 * float(ref.abs().max())
 
