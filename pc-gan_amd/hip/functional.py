@@ -25,7 +25,7 @@ def _fused_grad_target(p):
 
 
 def _pack_cache(p):
-    """Per-parameter dict holding the packed copies of a conv weight (see ops._packed_weights)."""
+    """Per-parameter dict holding the packed copies of a conv weight, one per packed form in use (see ops._packed_weights, ops._PACK_FORMS)."""
     if p is None or not isinstance(p, torch.nn.Parameter):
         return None
     c = p.__dict__.get('_pcgan_pack')
@@ -35,6 +35,34 @@ def _pack_cache(p):
 
 
 # ---------------------------------------------------------------------------- conv
+def _conv_backward(ctx, x, dy, w, wgrad_operands, cfg, dgrad):
+    """What the backward passes of _Conv2dFn and _ConvTranspose2dFn share; returns (dx, dw, db).  dgrad() is the Function's own
+    data-gradient call; the weight gradient takes wgrad_operands = (x, dy), swapped for the transposed conv, and cfg = (stride, pad,
+    pad_mode); the bias gradient is the channel sum of dy for both."""
+    if ctx.x_amax is not None and ctx.x_amax[0] == x._version and '_pcgan_amax' not in x.__dict__:
+        x._pcgan_amax = ctx.x_amax      # operand maxima its producer left (saved in forward: a saved tensor comes back without them)
+    want_x = ctx.needs_input_grad[0]
+    want_w = ctx.needs_input_grad[1]
+    want_b = ctx.has_bias and ctx.needs_input_grad[2]
+    wt = _fused_grad_target(ctx.params[0]) if want_w else None
+    bt = _fused_grad_target(ctx.params[1]) if want_b else None
+
+    def param_grads():
+        dw = ops.conv2d_bwd_weight(*wgrad_operands, tuple(w.shape), *cfg, accumulate_into=wt) if want_w else None
+        db = ops.channel_sum(dy, accumulate_into=bt) if want_b else None
+        return (dw if wt is None else None), (db if bt is None else None)
+
+    if ops.SIDE_STREAM and (not want_w or wt is not None) and (not want_b or bt is not None) and (want_w or want_b):
+        # both go straight into the optimizer's gradient buffer: nobody in this backward pass reads them.  Forked BEFORE the data
+        # gradient is queued, so the two kernels of this layer may run side by side (all accumulations into that buffer are issued
+        # in order on the one parameter-gradient stream).
+        with ops.fork_side(x, dy):
+            param_grads()
+        return (dgrad() if want_x else None), None, None
+    dx = dgrad() if want_x else None
+    return (dx,) + param_grads()
+
+
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, pad, pad_mode, act, slope):
@@ -51,39 +79,12 @@ class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
-        if ctx.x_amax is not None and ctx.x_amax[0] == x._version and '_pcgan_amax' not in x.__dict__:
-            x._pcgan_amax = ctx.x_amax
         stride, pad, pad_mode, act, slope = ctx.cfg
         dy = _c(dy)
         if act != ACT_NONE:
             dy = ops.act_bwd(dy, y, act, slope)
-        dx = dw = db = None
-        want_w = ctx.needs_input_grad[1]
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        wt = _fused_grad_target(ctx.params[0]) if want_w else None
-        bt = _fused_grad_target(ctx.params[1]) if want_b else None
-        if ops.SIDE_STREAM and (not want_w or wt is not None) and (not want_b or bt is not None) and (want_w or want_b):
-            # both go straight into the optimizer's gradient buffer: nobody in this backward pass reads them.  Forked
-            # BEFORE the data gradient is queued, so the two kernels of this layer may run side by side.
-            with ops.fork_side(x, dy):
-                if want_w:
-                    ops.conv2d_bwd_weight(x, dy, tuple(w.shape), stride, pad, pad_mode, accumulate_into=wt)
-                if want_b:
-                    ops.channel_sum(dy, accumulate_into=bt)
-            if ctx.needs_input_grad[0]:
-                dx = ops.conv2d_bwd_data(dy, w, (x.shape[2], x.shape[3]), stride, pad, pad_mode, pack_cache=ctx.pack)
-            return dx, None, None, None, None, None, None, None
-        if ctx.needs_input_grad[0]:
-            dx = ops.conv2d_bwd_data(dy, w, (x.shape[2], x.shape[3]), stride, pad, pad_mode, pack_cache=ctx.pack)
-        if want_w:
-            dw = ops.conv2d_bwd_weight(x, dy, tuple(w.shape), stride, pad, pad_mode, accumulate_into=wt)
-            if wt is not None:
-                dw = None
-        if want_b:
-            db = ops.channel_sum(dy, accumulate_into=bt)
-            if bt is not None:
-                db = None
-        return dx, dw, db, None, None, None, None, None
+        return _conv_backward(ctx, x, dy, w, (x, dy), (stride, pad, pad_mode), lambda: ops.conv2d_bwd_data(
+            dy, w, (x.shape[2], x.shape[3]), stride, pad, pad_mode, pack_cache=ctx.pack)) + (None,) * 5
 
 
 class _ResBlockFn(torch.autograd.Function):
@@ -233,35 +234,9 @@ class _ConvTranspose2dFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         stride, pad = ctx.cfg
         dy = _c(dy)
-        if ctx.x_amax is not None and ctx.x_amax[0] == x._version and '_pcgan_amax' not in x.__dict__:
-            x._pcgan_amax = ctx.x_amax
-        dx = dw = db = None
-        want_w = ctx.needs_input_grad[1]
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        wt = _fused_grad_target(ctx.params[0]) if want_w else None
-        bt = _fused_grad_target(ctx.params[1]) if want_b else None
-        if ops.SIDE_STREAM and (not want_w or wt is not None) and (not want_b or bt is not None) and (want_w or want_b):
-            # as in _Conv2dFn: both go straight into the optimizer's gradient buffer, on the parameter-gradient stream (all
-            # accumulations into that buffer are issued in order on the one stream)
-            with ops.fork_side(x, dy):
-                if want_w:
-                    ops.conv2d_bwd_weight(dy, x, tuple(w.shape), stride, pad, 0, accumulate_into=wt)
-                if want_b:
-                    ops.channel_sum(dy, accumulate_into=bt)
-            if ctx.needs_input_grad[0]:
-                dx = ops.conv2d_fwd(dy, w, None, stride, pad, 0, pack_cache=ctx.pack)
-            return dx, None, None, None, None, None
-        if ctx.needs_input_grad[0]:
-            dx = ops.conv2d_fwd(dy, w, None, stride, pad, 0, pack_cache=ctx.pack)
-        if want_w:
-            dw = ops.conv2d_bwd_weight(dy, x, tuple(w.shape), stride, pad, 0, accumulate_into=wt)
-            if wt is not None:
-                dw = None
-        if want_b:
-            db = ops.channel_sum(dy, accumulate_into=bt)
-            if bt is not None:
-                db = None
-        return dx, dw, db, None, None, None
+        # (the weight gradient of the conv this is the data gradient of: operands swapped)
+        return _conv_backward(ctx, x, dy, w, (dy, x), (stride, pad, 0), lambda: ops.conv2d_fwd(
+            dy, w, None, stride, pad, 0, pack_cache=ctx.pack)) + (None,) * 3
 
 
 def conv_transpose2d(x, w, b=None, stride=2, pad=1, out_pad=1):

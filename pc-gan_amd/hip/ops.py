@@ -2,6 +2,7 @@
 torch's caching allocator (device memory plumbing only) and launch on torch's current
 stream.  No arithmetic happens in Python or in torch here.
 """
+import collections
 import ctypes
 import os
 
@@ -109,22 +110,13 @@ class fork_side(object):
 
     def __enter__(self):
         cur = torch.cuda.current_stream()
-        dev = cur.device
-        st = _side.get(dev)
-        if st is None:
-            st = _side[dev] = torch.cuda.Stream(device=dev)
+        st = side_stream_for(cur)
         st.wait_stream(cur)
         for t in self.tensors:
             t.record_stream(st)
         self.ctx = torch.cuda.stream(st)
         self.ctx.__enter__()
-        _side_state['dirty'] = True
-        if not _side_state['queued']:
-            try:    # join automatically when the running backward pass ends
-                torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
-                _side_state['queued'] = True
-            except Exception:      # not inside a backward pass (or no such hook): FusedAdam.step / zero_grad join
-                pass
+        mark_side_used()
         return st
 
     def __exit__(self, *exc):
@@ -140,13 +132,13 @@ def side_stream_for(cur):
 
 
 def mark_side_used():
-    """work was queued on the side stream by a composite call (which forks inside the library): join when the backward pass ends"""
+    """work was queued on the side stream (fork_side, or a composite call, which forks inside the library): join when the running backward pass ends"""
     _side_state['dirty'] = True
     if not _side_state['queued']:
         try:
             torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
             _side_state['queued'] = True
-        except Exception:
+        except Exception:      # not inside a backward pass (or no such hook): FusedAdam.step / zero_grad join
             pass
 
 
@@ -170,6 +162,14 @@ for _kv in os.environ.get('PCGAN_STREAM_ALIAS', '').split(','):
         STREAM_ALIAS[_kv.split(':')[0].strip()] = _kv.split(':')[1].strip()
 
 
+def _branch_stream(device, name):
+    """the stream of branch `name` on `device` (made on first use)"""
+    st = _branch.get((device, name))
+    if st is None:
+        st = _branch[(device, name)] = torch.cuda.Stream(device=device)
+    return st
+
+
 class branch(object):
     """with branch('E') as b: ... loss = f(...) ; b.join(loss): run the body on the named stream after everything
     queued so far on the current stream; join() makes the current stream wait and hands the tensors over.
@@ -186,10 +186,7 @@ class branch(object):
     def __enter__(self):
         if self.on:
             self.cur = torch.cuda.current_stream()
-            key = (self.cur.device, self.name)
-            st = _branch.get(key)
-            if st is None:
-                st = _branch[key] = torch.cuda.Stream(device=self.cur.device)
+            st = _branch_stream(self.cur.device, self.name)
             if self.after is None:
                 st.wait_stream(self.cur)
             else:
@@ -234,11 +231,7 @@ def upload_stream(device):
     device = torch.device(device)
     if device.index is None:
         device = torch.device('cuda', torch.cuda.current_device())
-    key = (device, STREAM_ALIAS.get('E', 'E'))
-    st = _branch.get(key)
-    if st is None:
-        st = _branch[key] = torch.cuda.Stream(device=device)
-    return st
+    return _branch_stream(device, STREAM_ALIAS.get('E', 'E'))
 
 
 def mark_ready(t, stream=None):
@@ -349,9 +342,9 @@ AMAX_STATS = {'attached': 0, 'computed': 0}     # operand maxima handed over by 
 ROUTE_STATS = {}     # (pass, route) -> number of convolution calls that took it: tests assert the kernels under test are the production ones
 
 
-def _count_route(pass_, route):
+def _count_route(pass_, route, n=1):
     k = (pass_, route)
-    ROUTE_STATS[k] = ROUTE_STATS.get(k, 0) + 1
+    ROUTE_STATS[k] = ROUTE_STATS.get(k, 0) + n
 
 
 def _want_maxima(dt, C):
@@ -418,9 +411,27 @@ def _audit_amax(x, claimed):
     AMAX_STATS['audited'] += 1
 
 
+# One record per packed-weight form, keyed by the cache pass: the library's byte query and pack call by name (both take the descriptor,
+# then `lib_pass` unless it is None) and, for the hgemm forms, the descriptor field that counts the weight rows whose maxima the pack
+# also writes (in front of the packed buffer in the call).
+_PackForm = collections.namedtuple('_PackForm', 'query pack lib_pass rows')
+_PACK_FORMS = {
+    _L.PASS_FWD: _PackForm('pcgan_conv2d_packed_bytes', 'pcgan_conv2d_pack_weights', _L.PASS_FWD, None),
+    _L.PASS_BWD_DATA: _PackForm('pcgan_conv2d_packed_bytes', 'pcgan_conv2d_pack_weights', _L.PASS_BWD_DATA, None),
+    PASS_FWD_BSPLIT: _PackForm('pcgan_conv2d_bsplit_packed_bytes', 'pcgan_conv2d_bsplit_pack', None, None),
+    PASS_BWD_BSPLIT: _PackForm('pcgan_conv2d_bsplit_dgrad_packed_bytes', 'pcgan_conv2d_bsplit_dgrad_pack', None, None),
+    PASS_FWD_HSPLIT: _PackForm('pcgan_conv2d_hsplit_packed_bytes', 'pcgan_conv2d_hsplit_pack', _L.PASS_FWD, None),
+    PASS_BWD_HSPLIT: _PackForm('pcgan_conv2d_hsplit_packed_bytes', 'pcgan_conv2d_hsplit_pack', _L.PASS_BWD_DATA, None),
+    PASS_FWD_HGEMM: _PackForm('pcgan_conv2d_packed_bytes', 'pcgan_conv2d_hgemm_pack', _L.PASS_FWD, 'K'),
+    PASS_BWD_HGEMM: _PackForm('pcgan_conv2d_packed_bytes', 'pcgan_conv2d_hgemm_pack', _L.PASS_BWD_DATA, 'C'),
+    PASS_FWD_THIN: _PackForm('pcgan_conv2d_thin_packed_bytes', 'pcgan_conv2d_thin_pack', _L.PASS_FWD, None),
+    PASS_BWD_THIN: _PackForm('pcgan_conv2d_thin_packed_bytes', 'pcgan_conv2d_thin_pack', _L.PASS_BWD_DATA, None),
+}
+
+
 def _packed_weights(lib, d, pass_, w, cache, want_rowmax=False):
-    """the packed copy of w for one pass; want_rowmax (hgemm route): (packed, rowmax) -- the pre-split pack also writes the largest
-    magnitude of every weight row, which the convolution's epilogue needs"""
+    """the packed copy of w for one pass; want_rowmax: (packed, rowmax) -- the pre-split pack of the hgemm forms also writes the largest
+    magnitude of every weight row, which the convolution's epilogue needs (None for every other form)"""
     key = (pass_, d.stride, d.pad, d.pad_mode, d.dtype)
     stamp = _weight_stamp(w)
     ent = cache.get(key)
@@ -429,19 +440,9 @@ def _packed_weights(lib, d, pass_, w, cache, want_rowmax=False):
             torch.cuda.current_stream().wait_event(ent[2])
         return (ent[1], ent[4]) if want_rowmax else ent[1]
     cur = torch.cuda.current_stream()
-    if pass_ in (PASS_FWD_HSPLIT, PASS_BWD_HSPLIT):
-        nb = int(lib.pcgan_conv2d_hsplit_packed_bytes(ctypes.byref(d), _L.PASS_FWD if pass_ == PASS_FWD_HSPLIT else _L.PASS_BWD_DATA))
-    elif pass_ == PASS_FWD_BSPLIT:
-        nb = int(lib.pcgan_conv2d_bsplit_packed_bytes(ctypes.byref(d)))
-    elif pass_ == PASS_BWD_BSPLIT:
-        nb = int(lib.pcgan_conv2d_bsplit_dgrad_packed_bytes(ctypes.byref(d)))
-    elif pass_ in (PASS_FWD_HGEMM, PASS_BWD_HGEMM):
-        nb = int(lib.pcgan_conv2d_packed_bytes(ctypes.byref(d), _L.PASS_FWD if pass_ == PASS_FWD_HGEMM else _L.PASS_BWD_DATA))
-    elif pass_ in (PASS_FWD_THIN, PASS_BWD_THIN):
-        nb = int(lib.pcgan_conv2d_thin_packed_bytes(ctypes.byref(d), _L.PASS_FWD if pass_ == PASS_FWD_THIN else _L.PASS_BWD_DATA))
-    else:
-        nb = int(lib.pcgan_conv2d_packed_bytes(ctypes.byref(d), pass_))
-    nb = max(nb, 256)
+    form = _PACK_FORMS[pass_]
+    head = (ctypes.byref(d),) if form.lib_pass is None else (ctypes.byref(d), form.lib_pass)
+    nb = max(int(getattr(lib, form.query)(*head)), 256)
     if ent is not None and ent[1].numel() == nb and ent[1].device == w.device:
         buf = ent[1]
         if ent[3] != cur.cuda_stream:      # re-pack into a buffer another stream may still be reading
@@ -450,25 +451,12 @@ def _packed_weights(lib, d, pass_, w, cache, want_rowmax=False):
     else:
         buf = _ws(nb, w.device)
     rowmax = None
-    if pass_ in (PASS_FWD_HGEMM, PASS_BWD_HGEMM):
-        rows = d.K if pass_ == PASS_FWD_HGEMM else d.C
+    if form.rows is not None:
+        rows = getattr(d, form.rows)
         rowmax = ent[4] if (ent is not None and len(ent) > 4 and ent[4] is not None and ent[4].numel() == rows and buf is ent[1]) else \
             torch.empty(rows, dtype=torch.float32, device=w.device)
-    if pass_ in (PASS_FWD_HSPLIT, PASS_BWD_HSPLIT):
-        _L.check(lib.pcgan_conv2d_hsplit_pack(ctypes.byref(d), _L.PASS_FWD if pass_ == PASS_FWD_HSPLIT else _L.PASS_BWD_DATA, _p(w), _p(buf),
-                                              _stream()), 'conv2d_hsplit_pack')
-    elif pass_ == PASS_FWD_BSPLIT:
-        _L.check(lib.pcgan_conv2d_bsplit_pack(ctypes.byref(d), _p(w), _p(buf), _stream()), 'conv2d_bsplit_pack')
-    elif pass_ == PASS_BWD_BSPLIT:
-        _L.check(lib.pcgan_conv2d_bsplit_dgrad_pack(ctypes.byref(d), _p(w), _p(buf), _stream()), 'conv2d_bsplit_dgrad_pack')
-    elif pass_ in (PASS_FWD_THIN, PASS_BWD_THIN):
-        _L.check(lib.pcgan_conv2d_thin_pack(ctypes.byref(d), _L.PASS_FWD if pass_ == PASS_FWD_THIN else _L.PASS_BWD_DATA, _p(w), _p(buf),
-                                            _stream()), 'conv2d_thin_pack')
-    elif pass_ in (PASS_FWD_HGEMM, PASS_BWD_HGEMM):
-        _L.check(lib.pcgan_conv2d_hgemm_pack(ctypes.byref(d), _L.PASS_FWD if pass_ == PASS_FWD_HGEMM else _L.PASS_BWD_DATA, _p(w), _p(rowmax),
-                                             _p(buf), _stream()), 'conv2d_hgemm_pack')
-    else:
-        _L.check(lib.pcgan_conv2d_pack_weights(ctypes.byref(d), pass_, _p(w), _p(buf), _stream()), 'conv2d_pack_weights')
+    out = (_p(buf),) if rowmax is None else (_p(rowmax), _p(buf))
+    _L.check(getattr(lib, form.pack)(*head, _p(w), *out, _stream()), form.pack[len('pcgan_'):])
     ev = torch.cuda.Event()
     ev.record(cur)
     cache[key] = (stamp, buf, ev, cur.cuda_stream, rowmax)
@@ -487,7 +475,7 @@ def clear_plans():
 
 
 class _Plan(object):
-    __slots__ = ('d', 'dref', 'P', 'Q', 'ws_bytes', 'route', 'pack_pass')
+    __slots__ = ('d', 'dref', 'P', 'Q', 'ws_bytes', 'route', 'pack_pass', 'amax', 'launch')
 
 
 # Non-finite sentinel of the fp16 route (include/pcgan_hip.h: pcgan_set_nonfinite_counter): one device word the kernels count
@@ -545,11 +533,76 @@ def check_nonfinite(where=''):
 
 
 # ---- the route table -------------------------------------------------------------------------------------------------------------------
-# Which kernel family a convolution call takes is DECLARED here: per pass an ordered list of (route, packed-weight pass, condition,
-# workspace query); the first entry whose condition holds wins.  A condition sees one context object `c`: the shape (N, C, H, W, K, R,
-# S, stride, pad, pad_mode, P, Q, dt, no_bias), the routing switches as they stand, the library handle and the descriptor.  The
-# measurements behind the order are in profiles/ (kernel dashboards, rNN_experiments.txt); the conditions that are pure shape limits of a
-# kernel live in the library (`*_supported`).
+# Which kernel family a convolution call takes is DECLARED here, once: per pass an ordered list of _Route records; the first whose
+# condition holds wins.  A record is (name, packed-weight pass = its key in _PACK_FORMS, condition, workspace query, amax, launch):
+# `amax` says that the kernel scales its fp32 operands by their largest magnitudes (amax_of; bf16 tensors: one product, no scaling) and
+# `launch` makes the library call -- one signature per pass, `pmax` arguments None where the route takes no maxima, `wmax` the weight
+# row maxima of the hgemm pack.  A condition sees one context object `c`: the shape (N, C, H, W, K, R, S, stride, pad, pad_mode, P, Q,
+# dt, no_bias), the routing switches as they stand, the library handle and the descriptor.  The measurements behind the order are in
+# profiles/ (kernel dashboards, rNN_experiments.txt); the conditions that are pure shape limits of a kernel live in the library
+# (`*_supported`).  To add a route: one record here, and one _PACK_FORMS entry if it has a packed form of its own.
+_Route = collections.namedtuple('_Route', 'name pack_pass cond ws_bytes amax launch')
+
+
+def _n(t):
+    return t.numel() if t is not None else 0
+
+
+def _fwd_hsplit(lib, d, x, xmax, pk, wmax, bias, y, act, slope, ws):
+    _L.check(lib.pcgan_conv2d_fwd_hsplit(d, _p(x), _p(xmax), _n(xmax), _p(pk), _p(bias), _p(y), act, slope, _stream()), 'conv2d_fwd_hsplit')
+
+
+def _fwd_hgemm(lib, d, x, xmax, pk, wmax, bias, y, act, slope, ws):
+    _L.check(lib.pcgan_conv2d_fwd_packed_hsplit(d, _p(x), _p(xmax), _n(xmax), _p(pk), _p(wmax), _p(bias), _p(y), act, slope, _p(ws), ws.numel(),
+                                                _stream()), 'conv2d_fwd_packed_hsplit')
+
+
+def _fwd_bsplit(lib, d, x, xmax, pk, wmax, bias, y, act, slope, ws):
+    _L.check(lib.pcgan_conv2d_fwd_bsplit(d, _p(x), _p(pk), _p(bias), _p(y), act, slope, _stream()), 'conv2d_fwd_bsplit')
+
+
+def _fwd_thin(lib, d, x, xmax, pk, wmax, bias, y, act, slope, ws):
+    _L.check(lib.pcgan_conv2d_fwd_thin(d, _p(x), _p(xmax), _n(xmax), _p(pk), _p(bias), _p(y), act, slope, _stream()), 'conv2d_fwd_thin')
+
+
+def _fwd_packed(lib, d, x, xmax, pk, wmax, bias, y, act, slope, ws):
+    _L.check(lib.pcgan_conv2d_fwd_packed(d, _p(x), _p(pk), _p(bias), _p(y), act, slope, _p(ws), ws.numel(), _stream()), 'conv2d_fwd_packed')
+
+
+def _dgrad_hsplit(lib, d, dy, dmax, pk, wmax, bias, dx, ws):
+    _L.check(lib.pcgan_conv2d_bwd_data_hsplit(d, _p(dy), _p(dmax), _n(dmax), _p(pk), _p(dx), _stream()), 'conv2d_bwd_data_hsplit')
+
+
+def _dgrad_bsplit(lib, d, dy, dmax, pk, wmax, bias, dx, ws):
+    _L.check(lib.pcgan_conv2d_bwd_data_bsplit(d, _p(dy), _p(pk), _p(dx), _stream()), 'conv2d_bwd_data_bsplit')
+
+
+def _dgrad_hgemm(lib, d, dy, dmax, pk, wmax, bias, dx, ws):
+    _L.check(lib.pcgan_conv2d_bwd_data_packed_hsplit(d, _p(dy), _p(dmax), _n(dmax), _p(pk), _p(wmax), _p(bias), _p(dx), _p(ws), ws.numel(),
+                                                     _stream()), 'conv2d_bwd_data_packed_hsplit')
+
+
+def _dgrad_thin(lib, d, dy, dmax, pk, wmax, bias, dx, ws):
+    _L.check(lib.pcgan_conv2d_bwd_data_thin(d, _p(dy), _p(dmax), _n(dmax), _p(pk), _p(dx), _p(ws), ws.numel(), _stream()), 'conv2d_bwd_data_thin')
+
+
+def _dgrad_packed(lib, d, dy, dmax, pk, wmax, bias, dx, ws):
+    _L.check(lib.pcgan_conv2d_bwd_data_packed(d, _p(dy), _p(pk), _p(bias), _p(dx), _p(ws), ws.numel(), _stream()), 'conv2d_bwd_data_packed')
+
+
+def _wgrad_hsplit(lib, d, x, xmax, dy, dmax, dw, acc, ws):
+    _L.check(lib.pcgan_conv2d_bwd_weight_hsplit(d, _p(x), _p(xmax), _n(xmax), _p(dy), _p(dmax), _n(dmax), _p(dw), acc, _p(ws), ws.numel(),
+                                                _stream()), 'conv2d_bwd_weight_hsplit')
+
+
+def _wgrad_bsplit(lib, d, x, xmax, dy, dmax, dw, acc, ws):
+    _L.check(lib.pcgan_conv2d_bwd_weight_bsplit(d, _p(x), _p(dy), _p(dw), acc, _p(ws), ws.numel(), _stream()), 'conv2d_bwd_weight_bsplit')
+
+
+def _wgrad_generic(lib, d, x, xmax, dy, dmax, dw, acc, ws):
+    _L.check(lib.pcgan_conv2d_bwd_weight(d, _p(x), _p(dy), _p(dw), acc, _p(ws), ws.numel(), _stream()), 'conv2d_bwd_weight')
+
+
 class _RouteCtx(object):
     pass
 
@@ -565,30 +618,34 @@ def _fills_chip(c):
 
 _FWD_ROUTES = (
     # residual-block convolutions, fp32 tensors: window kernel, two fp16 pieces
-    ('hsplit', PASS_FWD_HSPLIT, lambda c: _fills_chip(c) and c.K % 128 == 0 and c.lib.pcgan_conv2d_bsplit_supported(c.dref) and c.f16
-     and c.lib.pcgan_conv2d_hsplit_supported(c.dref, _L.PASS_FWD), _ws_generic(_L.PASS_FWD)),
+    _Route('hsplit', PASS_FWD_HSPLIT, lambda c: _fills_chip(c) and c.K % 128 == 0 and c.lib.pcgan_conv2d_bsplit_supported(c.dref) and c.f16
+           and c.lib.pcgan_conv2d_hsplit_supported(c.dref, _L.PASS_FWD), _ws_generic(_L.PASS_FWD), True, _fwd_hsplit),
     # every other fp32 convolution with a multiple of 16 gathered channels: packed implicit GEMM, two fp16 pieces (before the three-piece
     # kernel below: the encoder's 128-channel 28x28 layers were on its six products per term, 0.062 ms against 0.047)
-    ('hgemm', PASS_FWD_HGEMM, lambda c: c.f16 and HGEMM and c.lib.pcgan_conv2d_hgemm_supported(c.dref, _L.PASS_FWD), _ws_generic(_L.PASS_FWD)),
+    _Route('hgemm', PASS_FWD_HGEMM, lambda c: c.f16 and HGEMM and c.lib.pcgan_conv2d_hgemm_supported(c.dref, _L.PASS_FWD), _ws_generic(_L.PASS_FWD),
+           True, _fwd_hgemm),
     # three-piece bf16 split (PCGAN_SPLIT=bf16) / bf16 tensors: window or per-tap kernel
-    ('bsplit', PASS_FWD_BSPLIT, lambda c: _fills_chip(c) and c.K % 128 == 0 and c.lib.pcgan_conv2d_bsplit_supported(c.dref), _ws_generic(_L.PASS_FWD)),
+    _Route('bsplit', PASS_FWD_BSPLIT, lambda c: _fills_chip(c) and c.K % 128 == 0 and c.lib.pcgan_conv2d_bsplit_supported(c.dref), _ws_generic(_L.PASS_FWD),
+           False, _fwd_bsplit),
     # <= 4 gathered channels (7x7 stems, first PatchGAN layer)
-    ('thin', PASS_FWD_THIN, lambda c: c.f16 and THIN and (THIN_MASK & (1 if c.stride == 1 else 2)) and c.lib.pcgan_conv2d_thin_supported(c.dref, _L.PASS_FWD),
-     _ws_generic(_L.PASS_FWD)),
-    ('packed', _L.PASS_FWD, lambda c: True, _ws_generic(_L.PASS_FWD)),       # fp32-MFMA implicit GEMM / small-M kernels
+    _Route('thin', PASS_FWD_THIN, lambda c: c.f16 and THIN and (THIN_MASK & (1 if c.stride == 1 else 2)) and c.lib.pcgan_conv2d_thin_supported(c.dref, _L.PASS_FWD),
+           _ws_generic(_L.PASS_FWD), True, _fwd_thin),
+    _Route('packed', _L.PASS_FWD, lambda c: True, _ws_generic(_L.PASS_FWD), False, _fwd_packed),       # fp32-MFMA implicit GEMM / small-M kernels
 )
 
 _DGRAD_ROUTES = (
-    ('hsplit', PASS_BWD_HSPLIT, lambda c: c.split and c.no_bias and c.C % 128 == 0 and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS
-     and c.lib.pcgan_conv2d_bsplit_dgrad_supported(c.dref) and c.f16 and c.lib.pcgan_conv2d_hsplit_supported(c.dref, _L.PASS_BWD_DATA),
-     _ws_generic(_L.PASS_BWD_DATA)),
-    ('bsplit', PASS_BWD_BSPLIT, lambda c: c.split and c.no_bias and c.C % 128 == 0 and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS
-     and c.lib.pcgan_conv2d_bsplit_dgrad_supported(c.dref), _ws_generic(_L.PASS_BWD_DATA)),
-    ('hgemm', PASS_BWD_HGEMM, lambda c: c.f16 and HGEMM and c.lib.pcgan_conv2d_hgemm_supported(c.dref, _L.PASS_BWD_DATA), _ws_generic(_L.PASS_BWD_DATA)),
+    _Route('hsplit', PASS_BWD_HSPLIT, lambda c: c.split and c.no_bias and c.C % 128 == 0 and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS
+           and c.lib.pcgan_conv2d_bsplit_dgrad_supported(c.dref) and c.f16 and c.lib.pcgan_conv2d_hsplit_supported(c.dref, _L.PASS_BWD_DATA),
+           _ws_generic(_L.PASS_BWD_DATA), True, _dgrad_hsplit),
+    _Route('bsplit', PASS_BWD_BSPLIT, lambda c: c.split and c.no_bias and c.C % 128 == 0 and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS
+           and c.lib.pcgan_conv2d_bsplit_dgrad_supported(c.dref), _ws_generic(_L.PASS_BWD_DATA), False, _dgrad_bsplit),
+    _Route('hgemm', PASS_BWD_HGEMM, lambda c: c.f16 and HGEMM and c.lib.pcgan_conv2d_hgemm_supported(c.dref, _L.PASS_BWD_DATA), _ws_generic(_L.PASS_BWD_DATA),
+           True, _dgrad_hgemm),
     # the data gradient of the 64 -> 3 head as a forward-form convolution (no pack cache: the generic call; needs the padded-grid workspace)
-    ('thin', PASS_BWD_THIN, lambda c: c.f16 and THIN and (THIN_MASK & 4) and c.no_bias and c.lib.pcgan_conv2d_thin_supported(c.dref, _L.PASS_BWD_DATA),
-     lambda c: max(int(c.lib.pcgan_conv2d_workspace_bytes(c.dref, _L.PASS_BWD_DATA)), int(c.lib.pcgan_conv2d_thin_workspace_bytes(c.dref, _L.PASS_BWD_DATA)))),
-    ('packed', _L.PASS_BWD_DATA, lambda c: True, _ws_generic(_L.PASS_BWD_DATA)),
+    _Route('thin', PASS_BWD_THIN, lambda c: c.f16 and THIN and (THIN_MASK & 4) and c.no_bias and c.lib.pcgan_conv2d_thin_supported(c.dref, _L.PASS_BWD_DATA),
+           lambda c: max(int(c.lib.pcgan_conv2d_workspace_bytes(c.dref, _L.PASS_BWD_DATA)), int(c.lib.pcgan_conv2d_thin_workspace_bytes(c.dref, _L.PASS_BWD_DATA))),
+           True, _dgrad_thin),
+    _Route('packed', _L.PASS_BWD_DATA, lambda c: True, _ws_generic(_L.PASS_BWD_DATA), False, _dgrad_packed),
 )
 
 
@@ -612,10 +669,10 @@ def _wgrad_on_matrix_pipe(c):
 
 
 _WGRAD_ROUTES = (
-    ('hsplit', None, _wgrad_on_matrix_pipe, lambda c: int(c.lib.pcgan_conv2d_hsplit_wgrad_workspace_bytes(c.dref))),
-    ('bsplit', None, lambda c: c.split and c.K in (128, 256) and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS and c.lib.pcgan_conv2d_bsplit_wgrad_supported(c.dref),
-     lambda c: int(c.lib.pcgan_conv2d_bsplit_wgrad_workspace_bytes(c.dref))),
-    ('generic', None, lambda c: True, _ws_generic(_L.PASS_BWD_WEIGHT)),      # fp32-MFMA / small-M weight-gradient kernels
+    _Route('hsplit', None, _wgrad_on_matrix_pipe, lambda c: int(c.lib.pcgan_conv2d_hsplit_wgrad_workspace_bytes(c.dref)), True, _wgrad_hsplit),
+    _Route('bsplit', None, lambda c: c.split and c.K in (128, 256) and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS and c.lib.pcgan_conv2d_bsplit_wgrad_supported(c.dref),
+           lambda c: int(c.lib.pcgan_conv2d_bsplit_wgrad_workspace_bytes(c.dref)), False, _wgrad_bsplit),
+    _Route('generic', None, lambda c: True, _ws_generic(_L.PASS_BWD_WEIGHT), False, _wgrad_generic),      # fp32-MFMA / small-M weight-gradient kernels
 )
 ROUTE_TABLE = {_L.PASS_FWD: _FWD_ROUTES, _L.PASS_BWD_DATA: _DGRAD_ROUTES, _L.PASS_BWD_WEIGHT: _WGRAD_ROUTES}
 
@@ -637,9 +694,10 @@ def _plan(pass_, N, C, H, W, K, R, S, stride, pad, pad_mode, dt, no_bias=True):
     c.lib, c.dref = lib, p.dref
     c.split = BF16X6 or dt == BF16          # the matrix-pipe split kernels may take the call (always for bf16 tensors)
     c.f16 = HSPLIT and dt == F32            # fp32 tensors on the fp16 two-piece route
-    for route, pack_pass, cond, ws in ROUTE_TABLE[pass_]:
-        if cond(c):
-            p.route, p.pack_pass, p.ws_bytes = route, pack_pass, ws(c)
+    for r in ROUTE_TABLE[pass_]:
+        if r.cond(c):
+            p.route, p.pack_pass, p.ws_bytes = r.name, r.pack_pass, r.ws_bytes(c)
+            p.amax, p.launch = r.amax and dt == F32, r.launch      # (bound here: the per-call path does no second lookup)
             break
     _PLANS[key] = p
     return p
@@ -659,28 +717,9 @@ def conv2d_fwd(x, w, bias, stride, pad, pad_mode=0, act=ACT_NONE, slope=0.0, pac
     y = torch.empty((N, K, pl.P, pl.Q), dtype=x.dtype, device=x.device)
     ws = _ws(pl.ws_bytes, x.device)
     if pack_cache is not None:
-        if pl.route == 'hgemm':
-            pk, wmax = _packed_weights(lib, pl.d, pl.pack_pass, w, pack_cache, True)
-        else:
-            pk = _packed_weights(lib, pl.d, pl.pack_pass, w, pack_cache)
+        pk, wmax = _packed_weights(lib, pl.d, pl.pack_pass, w, pack_cache, True)
         _count_route('fwd', pl.route)
-        if pl.route == 'hgemm':
-            xmax = amax_of(x)
-            _L.check(lib.pcgan_conv2d_fwd_packed_hsplit(d, _p(x), _p(xmax), xmax.numel(), _p(pk), _p(wmax), _p(bias), _p(y), act,
-                                                        float(slope), _p(ws), ws.numel(), _stream()), 'conv2d_fwd_packed_hsplit')
-        elif pl.route == 'hsplit':
-            xmax = amax_of(x)
-            _L.check(lib.pcgan_conv2d_fwd_hsplit(d, _p(x), _p(xmax), xmax.numel(), _p(pk), _p(bias), _p(y), act, float(slope), _stream()),
-                     'conv2d_fwd_hsplit')
-        elif pl.route == 'bsplit':
-            _L.check(lib.pcgan_conv2d_fwd_bsplit(d, _p(x), _p(pk), _p(bias), _p(y), act, float(slope), _stream()), 'conv2d_fwd_bsplit')
-        elif pl.route == 'thin':
-            xmax = amax_of(x)
-            _L.check(lib.pcgan_conv2d_fwd_thin(d, _p(x), _p(xmax), xmax.numel(), _p(pk), _p(bias), _p(y), act, float(slope), _stream()),
-                     'conv2d_fwd_thin')
-        else:
-            _L.check(lib.pcgan_conv2d_fwd_packed(d, _p(x), _p(pk), _p(bias), _p(y), act, float(slope), _p(ws), ws.numel(), _stream()),
-                     'conv2d_fwd_packed')
+        pl.launch(lib, d, x, amax_of(x) if pl.amax else None, pk, wmax, bias, y, act, float(slope), ws)
         return y
     _L.check(lib.pcgan_conv2d_fwd(d, _p(x), _p(w), _p(bias), _p(y), act, float(slope), _p(ws), ws.numel(), _stream()), 'conv2d_fwd')
     return y
@@ -701,27 +740,9 @@ def conv2d_bwd_data(dy, w, in_hw, stride, pad, pad_mode=0, bias=None, pack_cache
     dx = torch.empty((N, C, H, W), dtype=dy.dtype, device=dy.device)
     ws = _ws(pl.ws_bytes, dy.device)
     if pack_cache is not None:
-        if pl.route == 'hgemm':
-            pk, wmax = _packed_weights(lib, pl.d, pl.pack_pass, w, pack_cache, True)
-        else:
-            pk = _packed_weights(lib, pl.d, pl.pack_pass, w, pack_cache)
+        pk, wmax = _packed_weights(lib, pl.d, pl.pack_pass, w, pack_cache, True)
         _count_route('dgrad', pl.route)
-        if pl.route == 'hsplit':
-            dmax = amax_of(dy)
-            _L.check(lib.pcgan_conv2d_bwd_data_hsplit(d, _p(dy), _p(dmax), dmax.numel(), _p(pk), _p(dx), _stream()), 'conv2d_bwd_data_hsplit')
-        elif pl.route == 'bsplit':
-            _L.check(lib.pcgan_conv2d_bwd_data_bsplit(d, _p(dy), _p(pk), _p(dx), _stream()), 'conv2d_bwd_data_bsplit')
-        elif pl.route == 'thin':
-            dmax = amax_of(dy)
-            _L.check(lib.pcgan_conv2d_bwd_data_thin(d, _p(dy), _p(dmax), dmax.numel(), _p(pk), _p(dx), _p(ws), ws.numel(), _stream()),
-                     'conv2d_bwd_data_thin')
-        elif pl.route == 'hgemm':
-            dmax = amax_of(dy)
-            _L.check(lib.pcgan_conv2d_bwd_data_packed_hsplit(d, _p(dy), _p(dmax), dmax.numel(), _p(pk), _p(wmax), _p(bias), _p(dx),
-                                                             _p(ws), ws.numel(), _stream()), 'conv2d_bwd_data_packed_hsplit')
-        else:
-            _L.check(lib.pcgan_conv2d_bwd_data_packed(d, _p(dy), _p(pk), _p(bias), _p(dx), _p(ws), ws.numel(), _stream()),
-                     'conv2d_bwd_data_packed')
+        pl.launch(lib, d, dy, amax_of(dy) if pl.amax else None, pk, wmax, bias, dx, ws)
         return dx
     _L.check(lib.pcgan_conv2d_bwd_data(d, _p(dy), _p(w), _p(bias), _p(dx), _p(ws), ws.numel(), _stream()), 'conv2d_bwd_data')
     return dx
@@ -752,19 +773,8 @@ def conv2d_bwd_weight(x, dy, w_shape, stride, pad, pad_mode=0, accumulate_into=N
     acc = int(accumulate_into is not None)
     ws = _ws(pl.ws_bytes, x.device)
     _count_route('wgrad', pl.route)
-    if pl.route == 'hsplit':
-        if dt == F32:
-            xmax, dmax = amax_of(x), amax_of(dy)
-            nx, nd = xmax.numel(), dmax.numel()
-        else:            # bf16 tensors: one product, no scaling
-            xmax = dmax = None
-            nx = nd = 0
-        _L.check(lib.pcgan_conv2d_bwd_weight_hsplit(d, _p(x), _p(xmax), nx, _p(dy), _p(dmax), nd, _p(dw), acc,
-                                                    _p(ws), ws.numel(), _stream()), 'conv2d_bwd_weight_hsplit')
-    elif pl.route == 'bsplit':
-        _L.check(lib.pcgan_conv2d_bwd_weight_bsplit(d, _p(x), _p(dy), _p(dw), acc, _p(ws), ws.numel(), _stream()), 'conv2d_bwd_weight_bsplit')
-    else:
-        _L.check(lib.pcgan_conv2d_bwd_weight(d, _p(x), _p(dy), _p(dw), acc, _p(ws), ws.numel(), _stream()), 'conv2d_bwd_weight')
+    xmax, dmax = (amax_of(x), amax_of(dy)) if pl.amax else (None, None)      # (bf16 tensors: one product, no scaling)
+    pl.launch(lib, d, x, xmax, dy, dmax, dw, acc, ws)
     return dw
 
 
@@ -814,6 +824,16 @@ def _fork_event(device):
     return ev
 
 
+def _wgrad_workspace(pl, device, side):
+    """one workspace for every weight-gradient launch of a composite shape: they run in issue order on the one side stream"""
+    key = (device, pl.ws_bytes)
+    ws = _WGRAD_WS.get(key)
+    if ws is None:
+        with torch.cuda.stream(side):
+            ws = _WGRAD_WS[key] = _ws(pl.ws_bytes, device)
+    return ws
+
+
 def resblock_fwd(pl, x, w1, b1, w2, b2, rm1, rv1, rm2, rv2, pack1, pack2):
     """returns out, (y1, h, y2, stats, amax, x_amax): everything the backward call needs besides x"""
     _chk(w1, b1, w2, b2, rm1, rv1, rm2, rv2)
@@ -828,9 +848,7 @@ def resblock_fwd(pl, x, w1, b1, w2, b2, rm1, rv1, rm2, rv2, pack1, pack2):
     amax = None if pl.half else torch.empty(2 * N * C, dtype=torch.float32, device=x.device)
     _L.check(lib.pcgan_resblock_fwd(pl.dref, _p(x), _p(xmax), 0 if pl.half else xmax.numel(), _p(pk1), _p(b1), _p(pk2), _p(b2), _p(rm1), _p(rv1),
                                     _p(rm2), _p(rv2), _p(y1), _p(h), _p(y2), _p(out), _p(stats), _p(amax), _stream()), 'resblock_fwd')
-    route = 'bsplit' if pl.half else 'hsplit'
-    _count_route('fwd', route)
-    _count_route('fwd', route)
+    _count_route('fwd', 'bsplit' if pl.half else 'hsplit', 2)
     COMPOSITE_STATS['fwd'] += 1
     if not pl.half:
         _attach_amax(out, amax[N * C:])
@@ -848,11 +866,7 @@ def resblock_bwd(pl, dout, x, saved, w1, w2, dw1, db1, dw2, db2, pack1, pack2):
     pk2b = _packed_weights(lib, pl.conv, pl.bwd_pass, w2, pack2)
     cur = torch.cuda.current_stream()
     side = side_stream_for(cur)
-    wkey = (x.device, pl.ws_bytes)
-    ws = _WGRAD_WS.get(wkey)
-    if ws is None:     # one workspace for every weight-gradient launch of this shape: they run in issue order on the one side stream
-        with torch.cuda.stream(side):
-            ws = _WGRAD_WS[wkey] = _ws(pl.ws_bytes, x.device)
+    ws = _wgrad_workspace(pl, x.device, side)
     dy2, dh, dy1, dx = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     scratch = torch.empty(5 * N * C, dtype=torch.float32, device=x.device)
     for t in (x, h, dy2, dy1, scratch, amax, xmax):      # read by the side stream after this call returns
@@ -861,9 +875,8 @@ def resblock_bwd(pl, dout, x, saved, w1, w2, dw1, db1, dw2, db2, pack1, pack2):
     _L.check(lib.pcgan_resblock_bwd(pl.dref, _p(dout), _p(x), _p(xmax), 0 if pl.half else xmax.numel(), _p(y1), _p(h), _p(amax), _p(y2), _p(stats), _p(pk1b),
                                     _p(pk2b), _p(dw1), _p(db1), _p(dw2), _p(db2), _p(dy2), _p(dh), _p(dy1), _p(dx), _p(scratch), _p(ws),
                                     ws.numel(), _vp(cur.cuda_stream), _vp(side.cuda_stream), _fork_event(x.device)), 'resblock_bwd')
-    for _ in range(2):
-        _count_route('dgrad', 'bsplit' if pl.half else 'hsplit')
-        _count_route('wgrad', 'hsplit')
+    _count_route('dgrad', 'bsplit' if pl.half else 'hsplit', 2)
+    _count_route('wgrad', 'hsplit', 2)
     if not pl.half:
         AMAX_STATS['attached'] += 6        # (x, h, dy2 x 2, dy1 x 2: the operand maxima all came from the norm kernels)
     PLANE_SUM_STATS['fused'] += 2
@@ -899,8 +912,7 @@ def restrunk_fwd(pl, x, blocks):
                                     _ptr_array(pk2), _ptr_array([b[3] for b in blocks]), _ptr_array([b[4] for b in blocks]),
                                     _ptr_array([b[5] for b in blocks]), _ptr_array([b[6] for b in blocks]), _ptr_array([b[7] for b in blocks]),
                                     _p(y1), _p(h), _p(y2), _p(out), _p(stats), _p(amax), _stream()), 'restrunk_fwd')
-    rk = ('fwd', 'bsplit' if pl.half else 'hsplit')
-    ROUTE_STATS[rk] = ROUTE_STATS.get(rk, 0) + 2 * nb
+    _count_route('fwd', 'bsplit' if pl.half else 'hsplit', 2 * nb)
     COMPOSITE_STATS['fwd'] += nb
     COMPOSITE_STATS['trunk_fwd'] = COMPOSITE_STATS.get('trunk_fwd', 0) + 1
     last = out[nb - 1]
@@ -922,11 +934,7 @@ def restrunk_bwd(pl, dout, x, saved, blocks):
     pk2b = [_packed_weights(lib, pl.conv, pl.bwd_pass, b[1], b[7]) for b in blocks]
     cur = torch.cuda.current_stream()
     side = side_stream_for(cur)
-    wkey = (x.device, pl.ws_bytes)
-    ws = _WGRAD_WS.get(wkey)
-    if ws is None:
-        with torch.cuda.stream(side):
-            ws = _WGRAD_WS[wkey] = _ws(pl.ws_bytes, x.device)
+    ws = _wgrad_workspace(pl, x.device, side)
     shape = (nb,) + tuple(x.shape)
     dy2, dy1 = torch.empty(shape, dtype=x.dtype, device=x.device), torch.empty(shape, dtype=x.dtype, device=x.device)
     dh, dx = torch.empty_like(x), torch.empty_like(x)
@@ -940,9 +948,8 @@ def restrunk_bwd(pl, dout, x, saved, blocks):
                                     _ptr_array([b[4] for b in blocks]), _ptr_array([b[5] for b in blocks]), _p(dy2), _p(dh), _p(dy1), _p(dxs),
                                     _p(dx), _p(scratch), _p(ws), ws.numel(), _vp(cur.cuda_stream), _vp(side.cuda_stream),
                                     _fork_event(x.device)), 'restrunk_bwd')
-    dk = ('dgrad', 'bsplit' if pl.half else 'hsplit')
-    ROUTE_STATS[dk] = ROUTE_STATS.get(dk, 0) + 2 * nb
-    ROUTE_STATS[('wgrad', 'hsplit')] = ROUTE_STATS.get(('wgrad', 'hsplit'), 0) + 2 * nb
+    _count_route('dgrad', 'bsplit' if pl.half else 'hsplit', 2 * nb)
+    _count_route('wgrad', 'hsplit', 2 * nb)
     if not pl.half:
         AMAX_STATS['attached'] += 6 * nb
     PLANE_SUM_STATS['fused'] += 2 * nb

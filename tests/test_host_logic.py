@@ -224,3 +224,54 @@ def test_declared_route_table_for_the_benchmark_layers():
     # bf16 tensors: the one-product forms
     assert tuple(ops._plan(ps, 32, 256, 32, 32, 256, 3, 3, 1, 1, 1, L.BF16).route for ps in (L.PASS_FWD, L.PASS_BWD_DATA, L.PASS_BWD_WEIGHT)) == \
         ('bsplit', 'bsplit', 'hsplit')
+
+
+# The sweep of tests/golden/route_plans.json: (C, H, W, K, R, S, stride, pad, pad_mode) of the layers above, the residual layer at three
+# sizes and the generator's first transposed convolution (256 -> 128, written as the convolution whose data gradient it is).
+ROUTE_SWEEP_LAYERS = {
+    'G.res': (256, 32, 32, 256, 3, 3, 1, 1, 1), 'G.stem': (4, 128, 128, 64, 7, 7, 1, 3, 1), 'G.down1': (64, 128, 128, 128, 3, 3, 2, 1, 0),
+    'G.down2': (128, 64, 64, 256, 3, 3, 2, 1, 0), 'G.head': (64, 128, 128, 3, 7, 7, 1, 3, 1), 'D.c0': (4, 128, 128, 64, 4, 4, 2, 1, 0),
+    'D.c3': (256, 16, 16, 512, 4, 4, 1, 1, 0), 'D.c4': (512, 15, 15, 1, 4, 4, 1, 1, 0), 'E.conv1': (3, 224, 224, 64, 7, 7, 2, 3, 0),
+    'E.l1': (64, 56, 56, 64, 3, 3, 1, 1, 0), 'E.l4': (512, 7, 7, 512, 3, 3, 1, 1, 0), 'IP.c1': (3, 224, 224, 64, 11, 11, 4, 2, 0),
+    'G.res16': (256, 16, 16, 256, 3, 3, 1, 1, 1), 'G.res64': (256, 64, 64, 256, 3, 3, 1, 1, 1), 'G.up1': (128, 64, 64, 256, 3, 3, 2, 1, 0),
+}
+ROUTE_SWEEP_BATCHES = (1, 2, 32)
+ROUTE_SWEEP_SWITCHES = {
+    'default': {}, 'no_hsplit': {'HSPLIT': False}, 'no_hsplit_no_bf16x6': {'HSPLIT': False, 'BF16X6': False}, 'no_thin': {'THIN': False},
+    'no_hgemm': {'HGEMM': False}, 'bsplit_min_pixels_0': {'BSPLIT_MIN_PIXELS': 0},
+}
+
+
+def route_sweep_plans(ops, L):
+    """[route, pack_pass, ws_bytes] of every point of the sweep under the switches as they stand: layer x batch x (F32, BF16) x
+    (forward, data gradient without / with bias, weight gradient)"""
+    out = []
+    for shape in ROUTE_SWEEP_LAYERS.values():
+        for n in ROUTE_SWEEP_BATCHES:
+            for dt in (L.F32, L.BF16):
+                for ps, no_bias in ((L.PASS_FWD, True), (L.PASS_BWD_DATA, True), (L.PASS_BWD_DATA, False), (L.PASS_BWD_WEIGHT, True)):
+                    pl = ops._plan(ps, n, *shape, dt, no_bias)
+                    out.append([pl.route, pl.pack_pass, int(pl.ws_bytes)])
+    return out
+
+
+def test_route_plans_match_the_recorded_sweep(monkeypatch):
+    """hip/ops.py: route, packed-weight pass and workspace size of every `_plan` of the sweep, under each switch setting the suite uses,
+    against the recording made before the route records grew their launchers (tests/golden/route_plans.json).  The weight-gradient
+    workspaces depend on the CU count, which the library takes as 256 without a device: the MI355X's own."""
+    import json
+    from pcgan_amd.hip import ops, lib as L
+    monkeypatch.setattr(ops, '_sentinel', lambda: None)          # (no device word on the CPU)
+    with open(os.path.join(GOLD, 'route_plans.json')) as f:
+        gold = json.load(f)
+    assert gold['layers'] == list(ROUTE_SWEEP_LAYERS) and gold['batches'] == list(ROUTE_SWEEP_BATCHES)
+    assert list(gold['plans']) == list(ROUTE_SWEEP_SWITCHES)
+    for name, switches in ROUTE_SWEEP_SWITCHES.items():
+        with monkeypatch.context() as m:
+            for k, v in switches.items():
+                m.setattr(ops, k, v)
+            got = route_sweep_plans(ops, L)
+        want = gold['plans'][name]
+        assert len(got) == len(want) == len(ROUTE_SWEEP_LAYERS) * len(ROUTE_SWEEP_BATCHES) * 2 * 4
+        wrong = [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
+        assert not wrong, (name, wrong[:8])
