@@ -8,6 +8,8 @@
 // plane statistics of a channel (exact, order-fixed, no atomics).
 //
 // Reference: models/networks.py:22-34 (get_norm_layer), models/resnet.py:47-71.
+#include <type_traits>
+
 #include "common.h"
 
 namespace pcgan {
@@ -71,6 +73,62 @@ struct BnMergeOut {
     long long* batches;
     float momentum;
 };
+// sum of the N plane sums s1 / s2 of channel c by ONE wave: the arithmetic of bn_bwd_reduce_kernel (WT as in bn_merge_channel)
+template <bool WT>
+__device__ __forceinline__ void bn_sum_channel(const float* s1_nc, const float* s2_nc, float* s1_c, float* s2_c, int N, int C, int c, int lane) {
+    float a = 0.f, b = 0.f;
+    for (int n = lane; n < N; n += 64) {
+        a += WT ? ld_wt(s1_nc + n * C + c) : s1_nc[n * C + c];
+        b += WT ? ld_wt(s2_nc + n * C + c) : s2_nc[n * C + c];
+    }
+    a = wave_sum(a);
+    b = wave_sum(b);
+    if (lane == 0) {
+        s1_c[c] = a;
+        s2_c[c] = b;
+    }
+}
+
+// V consecutive elements as fp32 (V = 4: one 16-byte / 8-byte access, V = 1: scalar)
+template <int V, typename T>
+__device__ __forceinline__ void ldv(const T* p, float (&v)[V]) {
+    if (V == 4) {
+        const float4 t = ld4(p);
+        v[0] = t.x; v[1 % V] = t.y; v[2 % V] = t.z; v[3 % V] = t.w;
+    } else {
+        v[0] = ld1(p);
+    }
+}
+template <int V, typename T>
+__device__ __forceinline__ void stv(T* p, const float (&v)[V]) {
+    if (V == 4) st4(p, make_float4(v[0], v[1 % V], v[2 % V], v[3 % V]));
+    else st1(p, v[0]);
+}
+// the sum of such a group in the order every plane loop uses, (v0 + v1) + (v2 + v3), and its largest magnitude folded into am
+template <int V>
+__device__ __forceinline__ float vsum(const float (&v)[V]) {
+    return V == 4 ? (v[0] + v[1 % V]) + (v[2 % V] + v[3 % V]) : v[0];
+}
+template <int V>
+__device__ __forceinline__ float vabsmax(float am, const float (&v)[V]) {
+    return V == 4 ? fmaxf(fmaxf(am, fmaxf(fabsf(v[0]), fabsf(v[1 % V]))), fmaxf(fabsf(v[2 % V]), fabsf(v[3 % V]))) : fmaxf(am, fabsf(v[0]));
+}
+
+// a thread's share of sum x (SQ = false) or of sum (x - mean)^2 over a plane of n groups of V elements
+template <int V, bool SQ, typename T>
+__device__ __forceinline__ float plane_partial(const T* xp, int n, float mean) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        float v[V];
+        ldv<V>(xp + V * i, v);
+        if (SQ) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) v[e] = (v[e] - mean) * (v[e] - mean);
+        }
+        s += vsum<V>(v);
+    }
+    return s;
+}
 
 // one workgroup per plane; mean and M2 = sum (x - mean)^2 by an exact two-pass
 template <typename T>
@@ -80,29 +138,10 @@ __global__ void __launch_bounds__(256) plane_stats_kernel(const T* __restrict__ 
     __shared__ float scratch[16];
     const size_t plane = blockIdx.x;
     const T* xp = x + plane * (size_t)HW;
-    float s = 0.f;
-    if ((HW & 3) == 0) {
-        for (int i = threadIdx.x; i < (HW >> 2); i += blockDim.x) {
-            const float4 v = ld4(xp + 4 * i);
-            s += (v.x + v.y) + (v.z + v.w);
-        }
-    } else {
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) s += ld1(xp + i);
-    }
+    const bool v4 = (HW & 3) == 0;      // 128-bit accesses
+    const float s = v4 ? plane_partial<4, false>(xp, HW >> 2, 0.f) : plane_partial<1, false>(xp, HW, 0.f);
     const float mean = block_sum(s, scratch) / (float)HW;
-    float q = 0.f;
-    if ((HW & 3) == 0) {
-        for (int i = threadIdx.x; i < (HW >> 2); i += blockDim.x) {
-            const float4 v = ld4(xp + 4 * i);
-            const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    } else {
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const float a = ld1(xp + i) - mean;
-            q += a * a;
-        }
-    }
+    const float q = v4 ? plane_partial<4, true>(xp, HW >> 2, mean) : plane_partial<1, true>(xp, HW, mean);
     const float m2 = block_sum(q, scratch);
     if (threadIdx.x == 0) {
         if (tk.ticket != nullptr) {
@@ -183,6 +222,28 @@ __device__ __forceinline__ void plane_coeffs(const NormArgs& a, size_t plane, fl
     b = a.beta ? a.beta[c] : 0.f;
 }
 
+// y = act(x * sc + sh (+ residual)) over a plane of n groups of V elements; returns the thread's largest |y|
+template <int V, typename T>
+__device__ __forceinline__ float norm_act_plane(const NormArgs& a, const T* xp, const T* rp, T* yp, int n, float sc, float sh) {
+    float am = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        float v[V], r[V];
+        ldv<V>(xp + V * i, v);
+#pragma unroll
+        for (int e = 0; e < V; ++e) v[e] = v[e] * sc + sh;
+        if (rp) {
+            ldv<V>(rp + V * i, r);
+#pragma unroll
+            for (int e = 0; e < V; ++e) v[e] += r[e];
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) v[e] = act_apply(v[e], a.act, a.slope);
+        stv<V>(yp + V * i, v);
+        am = vabsmax<V>(am, v);
+    }
+    return am;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) norm_act_fwd_kernel(NormArgs a) {
     const size_t plane = blockIdx.x;
@@ -192,29 +253,7 @@ __global__ void __launch_bounds__(256) norm_act_fwd_kernel(NormArgs a) {
     const T* xp = (const T*)a.x + plane * (size_t)a.HW;
     const T* rp = a.residual ? (const T*)a.residual + plane * (size_t)a.HW : nullptr;
     T* yp = (T*)a.out + plane * (size_t)a.HW;
-    float am = 0.f;
-    if ((a.HW & 3) == 0) {
-        for (int i = threadIdx.x; i < (a.HW >> 2); i += blockDim.x) {
-            float4 v = ld4(xp + 4 * i);
-            v.x = v.x * sc + sh; v.y = v.y * sc + sh; v.z = v.z * sc + sh; v.w = v.w * sc + sh;
-            if (rp) {
-                const float4 r = ld4(rp + 4 * i);
-                v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-            }
-            v.x = act_apply(v.x, a.act, a.slope); v.y = act_apply(v.y, a.act, a.slope);
-            v.z = act_apply(v.z, a.act, a.slope); v.w = act_apply(v.w, a.act, a.slope);
-            st4(yp + 4 * i, v);
-            am = fmaxf(fmaxf(am, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-        }
-    } else {
-        for (int i = threadIdx.x; i < a.HW; i += blockDim.x) {
-            float v = ld1(xp + i) * sc + sh;
-            if (rp) v += ld1(rp + i);
-            v = act_apply(v, a.act, a.slope);
-            st1(yp + i, v);
-            am = fmaxf(am, fabsf(v));
-        }
-    }
+    float am = (a.HW & 3) == 0 ? norm_act_plane<4>(a, xp, rp, yp, a.HW >> 2, sc, sh) : norm_act_plane<1>(a, xp, rp, yp, a.HW, sc, sh);
     if (a.pmax) {      // plane maximum for the fp16 route of the convolution that reads y (see instnorm_fwd_fused_kernel)
         __shared__ float scratch[16];
         am = block_max(am, scratch);
@@ -254,22 +293,8 @@ __global__ void __launch_bounds__(256) norm_bwd_stats_kernel(NormArgs a, BnTicke
     if (tk.ticket != nullptr) {      // batch norm: the last arriver sums the channel's N plane sums (bn_bwd_reduce_kernel)
         __shared__ int last_flag;
         const int c = (int)(plane % (size_t)tk.C);
-        if (bn_last_arriver(tk, c, &last_flag) && threadIdx.x < 64) {
-            const int lane = threadIdx.x;
-            const float* s1_nc = (const float*)a.out;
-            const float* s2_nc = (const float*)a.out2;
-            float u = 0.f, v = 0.f;
-            for (int n = lane; n < tk.N; n += 64) {
-                u += ld_wt(s1_nc + n * tk.C + c);
-                v += ld_wt(s2_nc + n * tk.C + c);
-            }
-            u = wave_sum(u);
-            v = wave_sum(v);
-            if (lane == 0) {
-                s1_c[c] = u;
-                s2_c[c] = v;
-            }
-        }
+        if (bn_last_arriver(tk, c, &last_flag) && threadIdx.x < 64)
+            bn_sum_channel<true>((const float*)a.out, (const float*)a.out2, s1_c, s2_c, tk.N, tk.C, c, threadIdx.x);
     }
 }
 
@@ -277,18 +302,7 @@ __global__ void bn_bwd_reduce_kernel(const float* __restrict__ s1_nc, const floa
                                      float* __restrict__ s1_c, float* __restrict__ s2_c, int N, int C) {
     const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (c >= C) return;
-    const int lane = threadIdx.x & 63;
-    float a = 0.f, b = 0.f;
-    for (int n = lane; n < N; n += 64) {
-        a += s1_nc[n * C + c];
-        b += s2_nc[n * C + c];
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-        s1_c[c] = a;
-        s2_c[c] = b;
-    }
+    bn_sum_channel<false>(s1_nc, s2_nc, s1_c, s2_c, N, C, c, threadIdx.x & 63);
 }
 
 template <typename T>
@@ -338,22 +352,6 @@ __device__ __forceinline__ void bn_for_each(int N, int C, int HW, int c, F f) {
         const size_t base = ((size_t)n * C + c) * HW;
         for (int k = ln * V; k < HW; k += 64 * V) f(base + k);
     }
-}
-
-// V consecutive elements as fp32 (V = 4: one 16-byte / 8-byte access, V = 1: scalar)
-template <int V, typename T>
-__device__ __forceinline__ void ldv(const T* p, float (&v)[V]) {
-    if (V == 4) {
-        const float4 t = ld4(p);
-        v[0] = t.x; v[1 % V] = t.y; v[2 % V] = t.z; v[3 % V] = t.w;
-    } else {
-        v[0] = ld1(p);
-    }
-}
-template <int V, typename T>
-__device__ __forceinline__ void stv(T* p, const float (&v)[V]) {
-    if (V == 4) st4(p, make_float4(v[0], v[1 % V], v[2 % V], v[3 % V]));
-    else st1(p, v[0]);
 }
 
 template <int V, typename T>
@@ -473,34 +471,51 @@ __global__ void __launch_bounds__(256) bn_bwd_fused_kernel(const T* __restrict__
 // Fused instance norm: the whole (n,c) plane lives in the workgroup's registers, so forward is ONE read
 // + ONE write (statistics, normalise, residual, activation) and backward ONE read of dy/x(/y) + ONE write.
 // T threads x E float4 per thread cover planes up to T*E*4 elements (HW % 4 == 0).
+// The forward direction is written once, instnorm_fwd_plane, over a policy P that says who shares a plane: the thread takes float4
+// number first(), first() + step(), ... of it, sum() / max() reduce over the sharers (sum() valid in all of them, max() at least
+// where first() == 0, which is who stores the plane's results).
 // ------------------------------------------------------------------------------------------------
-template <int E, typename T>
-__global__ void __launch_bounds__(1024) instnorm_fwd_fused_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                                                                   T* __restrict__ y, float* __restrict__ mean_nc,
-                                                                   float* __restrict__ m2_nc, int HW, float eps, int act,
-                                                                   float slope, float* __restrict__ y_pmax) {
-    __shared__ float scratch[16];
-    const size_t plane = blockIdx.x;
-    const int NT = blockDim.x, n4 = HW >> 2;
+struct PlaneBlock {     // one workgroup per plane: every reduction makes a hop through 16 floats of LDS, between barriers
+    float* scratch;
+    __device__ __forceinline__ int first() const { return threadIdx.x; }
+    __device__ __forceinline__ int step() const { return blockDim.x; }
+    __device__ __forceinline__ float sum(float v) const { return block_sum(v, scratch); }
+    __device__ __forceinline__ float max(float v) const { return block_max(v, scratch); }
+};
+// Planes of up to 1024 elements (the residual blocks' 32x32 maps: 8192 planes per launch): ONE WAVE per plane, four planes per workgroup.
+// Every reduction is a wave reduction (no barrier, no LDS): the workgroup-per-plane form spends its time in three barrier
+// pairs per 4 KB plane.  Same arithmetic (exact two-pass mean / M2), other summation order.  Used with E = 4: 64 lanes x 4 float4.
+struct PlaneWave {
+    int lane;
+    __device__ __forceinline__ int first() const { return lane; }
+    __device__ __forceinline__ int step() const { return 64; }
+    __device__ __forceinline__ float sum(float v) const { return wave_sum(v); }
+    __device__ __forceinline__ float max(float v) const { return wave_max(v); }
+};
+
+template <int E, typename T, typename P>
+__device__ __forceinline__ void instnorm_fwd_plane(P p, size_t plane, const T* x, const T* res, T* y, float* mean_nc, float* m2_nc, int HW,
+                                                   float eps, int act, float slope, float* y_pmax) {
+    const int NT = p.step(), n4 = HW >> 2;
     const T* xp = x + plane * (size_t)HW;
     float4 v[E];
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
-        const int i = threadIdx.x + k * NT;
+        const int i = p.first() + k * NT;
         v[k] = i < n4 ? ld4(xp + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     }
-    const float mean = block_sum(s, scratch) / (float)HW;
+    const float mean = p.sum(s) / (float)HW;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
-        if (threadIdx.x + k * NT < n4) {
+        if (p.first() + k * NT < n4) {
             const float a = v[k].x - mean, b = v[k].y - mean, c = v[k].z - mean, d = v[k].w - mean;
             q += (a * a + b * b) + (c * c + d * d);
         }
     }
-    const float m2 = block_sum(q, scratch);
+    const float m2 = p.sum(q);
     const float rstd = rsqrtf(m2 / (float)HW + eps);
     const float sh = -mean * rstd;
     const T* rp = res ? res + plane * (size_t)HW : nullptr;
@@ -508,7 +523,7 @@ __global__ void __launch_bounds__(1024) instnorm_fwd_fused_kernel(const T* __res
     float am = 0.f;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
-        const int i = threadIdx.x + k * NT;
+        const int i = p.first() + k * NT;
         if (i < n4) {
             float4 o = make_float4(v[k].x * rstd + sh, v[k].y * rstd + sh, v[k].z * rstd + sh, v[k].w * rstd + sh);
             if (rp) {
@@ -521,18 +536,40 @@ __global__ void __launch_bounds__(1024) instnorm_fwd_fused_kernel(const T* __res
             am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
         }
     }
-    if (threadIdx.x == 0) {
-        mean_nc[plane] = mean;
-        m2_nc[plane] = m2;
-    }
     // largest magnitude of y over this plane: the fp16 route of the convolution that reads y scales by the largest of them
     // (amax.hip; a plain store per plane -- one atomic maximum for the tensor serialises 8192 workgroups on one address)
-    if (y_pmax) {
-        am = block_max(am, scratch);
-        if (threadIdx.x == 0) y_pmax[plane] = am;
+    if (y_pmax) am = p.max(am);
+    if (p.first() == 0) {
+        mean_nc[plane] = mean;
+        m2_nc[plane] = m2;
+        if (y_pmax) y_pmax[plane] = am;
     }
 }
 
+// The forward kernels: the workgroup form with E = 1 / 4 / 16, the wave form (four planes per workgroup).  __restrict__ lives here, on the kernels' pointers.
+template <int E, typename T>
+__global__ void __launch_bounds__(1024) instnorm_fwd_fused_kernel(const T* __restrict__ x, const T* __restrict__ res,
+                                                                   T* __restrict__ y, float* __restrict__ mean_nc,
+                                                                   float* __restrict__ m2_nc, int HW, float eps, int act,
+                                                                   float slope, float* __restrict__ y_pmax) {
+    __shared__ float scratch[16];
+    instnorm_fwd_plane<E, T>(PlaneBlock{scratch}, blockIdx.x, x, res, y, mean_nc, m2_nc, HW, eps, act, slope, y_pmax);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) instnorm_fwd_wave_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
+                                                                 float* __restrict__ mean_nc, float* __restrict__ m2_nc, int planes, int HW,
+                                                                 float eps, int act, float slope, float* __restrict__ y_pmax) {
+    const PlaneWave p{(int)(threadIdx.x & 63)};
+    const size_t plane = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (plane >= (size_t)planes) return;        // some waves of the last workgroup leave early: safe only because PlaneWave has no barrier
+    instnorm_fwd_plane<4, T>(p, plane, x, res, y, mean_nc, m2_nc, HW, eps, act, slope, y_pmax);
+}
+
+// The backward direction is still written out once per form.  Its sum of g * xhat, (gx*xx + gy*xy) + (gz*xz + gw*xw), is contracted
+// to fused multiply-adds only in the E = 16 kernel, and which product of a pair stays unfused there follows the operand order the
+// vectoriser happens to choose: with the body moved into a function shared by both forms that order flips, and dx of planes above
+// 16384 elements changes in the last bit.  Until the contraction is stated in the source the two forms keep their own text.
 template <int E, typename T>
 __global__ void __launch_bounds__(1024) instnorm_bwd_fused_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                                    const T* __restrict__ y, const float* __restrict__ mean_nc,
@@ -594,70 +631,6 @@ __global__ void __launch_bounds__(1024) instnorm_bwd_fused_kernel(const T* __res
     if (dx_pmax) {     // largest magnitude of dx over this plane, as in the forward kernel
         am = block_max(am, scratch);
         if (threadIdx.x == 0) dx_pmax[plane] = am;
-    }
-}
-
-// Planes of up to 1024 elements (the residual blocks' 32x32 maps: 8192 planes per launch): ONE WAVE per plane, four planes per workgroup.
-// Every reduction is a wave reduction (no barrier, no LDS): the workgroup-per-plane form above spends its time in three barrier
-// pairs per 4 KB plane.  Same arithmetic (exact two-pass mean / M2), other summation order.
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) instnorm_fwd_wave_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
-                                                                 float* __restrict__ mean_nc, float* __restrict__ m2_nc, int planes, int HW,
-                                                                 float eps, int act, float slope, float* __restrict__ y_pmax) {
-    const int lane = threadIdx.x & 63;
-    const size_t plane = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (plane >= (size_t)planes) return;
-    const int n4 = HW >> 2;
-    const T* xp = x + plane * (size_t)HW;
-    float4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = lane + k * 64;
-        v[k] = i < n4 ? ld4(xp + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-    }
-    const float mean = wave_sum(s) / (float)HW;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (lane + k * 64 < n4) {
-            const float a = v[k].x - mean, b = v[k].y - mean, c = v[k].z - mean, d = v[k].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-    const float m2 = wave_sum(q);
-    const float rstd = rsqrtf(m2 / (float)HW + eps);
-    const float sh = -mean * rstd;
-    const T* rp = res ? res + plane * (size_t)HW : nullptr;
-    T* yp = y + plane * (size_t)HW;
-    float am = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = lane + k * 64;
-        if (i < n4) {
-            float4 o = make_float4(v[k].x * rstd + sh, v[k].y * rstd + sh, v[k].z * rstd + sh, v[k].w * rstd + sh);
-            if (rp) {
-                const float4 r = ld4(rp + 4 * i);
-                o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-            }
-            o.x = act_apply(o.x, act, slope); o.y = act_apply(o.y, act, slope);
-            o.z = act_apply(o.z, act, slope); o.w = act_apply(o.w, act, slope);
-            st4(yp + 4 * i, o);
-            am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-        }
-    }
-    if (y_pmax) am = wave_max(am);
-    if (lane == 0) {
-        mean_nc[plane] = mean;
-        m2_nc[plane] = m2;
-        if (y_pmax) y_pmax[plane] = am;
     }
 }
 
@@ -734,6 +707,37 @@ static inline void fused_plan(int HW, int* T, int* E) {  // T: threads
 
 static inline int plane_threads(int HW) { return HW >= 1024 ? 256 : (HW >= 256 ? 128 : 64); }
 
+// NormArgs with what all four two-pass entry points share; every other field is null / 0 and is set by name at the call
+static NormArgs norm_args(const void* x, const float* mean, const float* var, int N, int C, int HW, int per_plane, float eps, int act,
+                          float slope) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.mean = mean; a.var = var;
+    a.N = N; a.C = C; a.HW = HW; a.per_plane = per_plane; a.eps = eps; a.act = act; a.slope = slope;
+    return a;
+}
+
+// The tier of a register-resident instance-norm launch (fused_plan's E and NT): launch(form, grid, block) with form.wave and form.E
+// compile-time constants, for both directions.
+template <bool W, int E_>
+struct InstnormForm {
+    static constexpr bool wave = W;
+    static constexpr int E = E_;
+};
+template <typename F>
+static void instnorm_dispatch(int E, int NT, int planes, F launch) {
+    if (E == 1 && planes >= 1024) launch(InstnormForm<true, 4>{}, dim3((planes + 3) / 4), dim3(256));      // small planes, many of them: one wave per plane
+    else if (E == 1) launch(InstnormForm<false, 1>{}, dim3(planes), dim3(NT));
+    else if (E == 4) launch(InstnormForm<false, 4>{}, dim3(planes), dim3(NT));
+    else launch(InstnormForm<false, 16>{}, dim3(planes), dim3(NT));
+}
+// the access width of the fused BatchNorm pair: launch(v) with v.value = V a compile-time constant
+template <typename F>
+static void bn_fused_dispatch(int HW, F launch) {
+    if ((HW & 3) == 0) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 1>{});
+}
+
 }  // namespace pcgan
 
 using namespace pcgan;
@@ -763,10 +767,8 @@ extern "C" int pcgan_bn_bwd_stats_reduced(const void* dy, const void* x, const v
                                           float slope, int dtype, pcgan_stream_t s) {
     PCGAN_CHECK(dy && x && mean_c && var_c && s1_nc && s2_nc && s1_c && s2_c && ticket && N > 0 && C > 0 && HW > 0, "bn_bwd_stats_reduced: bad arguments");
     PCGAN_CHECK(act == PCGAN_ACT_NONE || y, "bn_bwd_stats_reduced: activation mask needs y");
-    NormArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.y = y; a.dy = dy; a.mean = mean_c; a.var = var_c; a.out = s1_nc; a.out2 = s2_nc;
-    a.N = N; a.C = C; a.HW = HW; a.per_plane = 0; a.eps = eps; a.act = act; a.slope = slope;
+    NormArgs a = norm_args(x, mean_c, var_c, N, C, HW, 0, eps, act, slope);
+    a.y = y; a.dy = dy; a.out = s1_nc; a.out2 = s2_nc;
     const BnTicket tk{ticket, N, C};
     PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(norm_bwd_stats_kernel<T>, dim3(N * C), dim3(plane_threads(HW)), 0, (hipStream_t)s, a, tk, s1_c, s2_c));
     PCGAN_LAUNCH_CHECK();
@@ -798,10 +800,8 @@ extern "C" int pcgan_norm_act_fwd(const void* x, const float* mean, const float*
                                   const float* beta, const void* residual, void* y, float* y_pmax, int N, int C, int HW,
                                   int per_plane, float eps, int act, float slope, int dtype, pcgan_stream_t s) {
     PCGAN_CHECK(x && mean && var && y && N > 0 && C > 0 && HW > 0, "norm_act_fwd: bad arguments");
-    NormArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.mean = mean; a.var = var; a.gamma = gamma; a.beta = beta; a.residual = residual; a.out = y; a.pmax = y_pmax;
-    a.N = N; a.C = C; a.HW = HW; a.per_plane = per_plane; a.eps = eps; a.act = act; a.slope = slope;
+    NormArgs a = norm_args(x, mean, var, N, C, HW, per_plane, eps, act, slope);
+    a.gamma = gamma; a.beta = beta; a.residual = residual; a.out = y; a.pmax = y_pmax;
     PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(norm_act_fwd_kernel<T>, dim3(N * C), dim3(plane_threads(HW)), 0, (hipStream_t)s, a));
     PCGAN_LAUNCH_CHECK();
     return 0;
@@ -812,10 +812,8 @@ extern "C" int pcgan_norm_bwd_stats(const void* dy, const void* x, const void* y
                                     int per_plane, float eps, int act, float slope, int dtype, pcgan_stream_t s) {
     PCGAN_CHECK(dy && x && mean && var && s1_nc && s2_nc, "norm_bwd_stats: null pointer");
     PCGAN_CHECK(act == PCGAN_ACT_NONE || y, "norm_bwd_stats: activation mask needs y");
-    NormArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.y = y; a.dy = dy; a.mean = mean; a.var = var; a.out = s1_nc; a.out2 = s2_nc;
-    a.N = N; a.C = C; a.HW = HW; a.per_plane = per_plane; a.eps = eps; a.act = act; a.slope = slope;
+    NormArgs a = norm_args(x, mean, var, N, C, HW, per_plane, eps, act, slope);
+    a.y = y; a.dy = dy; a.out = s1_nc; a.out2 = s2_nc;
     PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(norm_bwd_stats_kernel<T>, dim3(N * C), dim3(plane_threads(HW)), 0, (hipStream_t)s, a));
     PCGAN_LAUNCH_CHECK();
     return 0;
@@ -836,11 +834,8 @@ extern "C" int pcgan_norm_bwd_apply(const void* dy, const void* x, const void* y
                                     int act, float slope, int dtype, pcgan_stream_t s) {
     PCGAN_CHECK(dy && x && mean && var && s1 && s2 && dx, "norm_bwd_apply: null pointer");
     PCGAN_CHECK(act == PCGAN_ACT_NONE || y, "norm_bwd_apply: activation mask needs y");
-    NormArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.y = y; a.dy = dy; a.mean = mean; a.var = var; a.gamma = gamma; a.s1 = s1; a.s2 = s2;
-    a.out = dx; a.out2 = d_residual; a.pmax = dx_pmax;
-    a.N = N; a.C = C; a.HW = HW; a.per_plane = per_plane; a.eps = eps; a.act = act; a.slope = slope;
+    NormArgs a = norm_args(x, mean, var, N, C, HW, per_plane, eps, act, slope);
+    a.y = y; a.dy = dy; a.gamma = gamma; a.s1 = s1; a.s2 = s2; a.out = dx; a.out2 = d_residual; a.pmax = dx_pmax;
     a.inv_cnt = 1.f / (per_plane ? (float)HW : (float)N * (float)HW);
     PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(norm_bwd_apply_kernel<T>, dim3(N * C), dim3(plane_threads(HW)), 0, (hipStream_t)s, a));
     PCGAN_LAUNCH_CHECK();
@@ -853,11 +848,11 @@ static void launch_instnorm_fwd(int E, int NT, int planes, hipStream_t st, const
     const T* xp = (const T*)x;
     const T* rp = (const T*)residual;
     T* yp = (T*)y;
-    if (E == 1 && planes >= 1024)      // small planes, many of them: one wave per plane
-        hipLaunchKernelGGL((instnorm_fwd_wave_kernel<T>), dim3((planes + 3) / 4), dim3(256), 0, st, xp, rp, yp, mean_nc, m2_nc, planes, HW, eps, act, slope, amax);
-    else if (E == 1) hipLaunchKernelGGL((instnorm_fwd_fused_kernel<1, T>), dim3(planes), dim3(NT), 0, st, xp, rp, yp, mean_nc, m2_nc, HW, eps, act, slope, amax);
-    else if (E == 4) hipLaunchKernelGGL((instnorm_fwd_fused_kernel<4, T>), dim3(planes), dim3(NT), 0, st, xp, rp, yp, mean_nc, m2_nc, HW, eps, act, slope, amax);
-    else hipLaunchKernelGGL((instnorm_fwd_fused_kernel<16, T>), dim3(planes), dim3(NT), 0, st, xp, rp, yp, mean_nc, m2_nc, HW, eps, act, slope, amax);
+    instnorm_dispatch(E, NT, planes, [&](auto form, dim3 grid, dim3 block) {
+        typedef decltype(form) F;
+        if constexpr (F::wave) hipLaunchKernelGGL((instnorm_fwd_wave_kernel<T>), grid, block, 0, st, xp, rp, yp, mean_nc, m2_nc, planes, HW, eps, act, slope, amax);
+        else hipLaunchKernelGGL((instnorm_fwd_fused_kernel<F::E, T>), grid, block, 0, st, xp, rp, yp, mean_nc, m2_nc, HW, eps, act, slope, amax);
+    });
 }
 
 extern "C" int pcgan_instnorm_fwd(const void* x, const void* residual, void* y, float* mean_nc, float* m2_nc, float* y_pmax, int N,
@@ -889,11 +884,11 @@ static void launch_instnorm_bwd(int E, int NT, int planes, hipStream_t st, const
     const T* xp = (const T*)x;
     const T* yp = (const T*)y;
     T* op = (T*)dx;
-    if (E == 1 && planes >= 1024)
-        hipLaunchKernelGGL((instnorm_bwd_wave_kernel<T>), dim3((planes + 3) / 4), dim3(256), 0, st, dp, xp, yp, mean_nc, m2_nc, op, dx_psum, planes, HW, eps, act, slope, amax);
-    else if (E == 1) hipLaunchKernelGGL((instnorm_bwd_fused_kernel<1, T>), dim3(planes), dim3(NT), 0, st, dp, xp, yp, mean_nc, m2_nc, op, dx_psum, HW, eps, act, slope, amax);
-    else if (E == 4) hipLaunchKernelGGL((instnorm_bwd_fused_kernel<4, T>), dim3(planes), dim3(NT), 0, st, dp, xp, yp, mean_nc, m2_nc, op, dx_psum, HW, eps, act, slope, amax);
-    else hipLaunchKernelGGL((instnorm_bwd_fused_kernel<16, T>), dim3(planes), dim3(NT), 0, st, dp, xp, yp, mean_nc, m2_nc, op, dx_psum, HW, eps, act, slope, amax);
+    instnorm_dispatch(E, NT, planes, [&](auto form, dim3 grid, dim3 block) {
+        typedef decltype(form) F;
+        if constexpr (F::wave) hipLaunchKernelGGL((instnorm_bwd_wave_kernel<T>), grid, block, 0, st, dp, xp, yp, mean_nc, m2_nc, op, dx_psum, planes, HW, eps, act, slope, amax);
+        else hipLaunchKernelGGL((instnorm_bwd_fused_kernel<F::E, T>), grid, block, 0, st, dp, xp, yp, mean_nc, m2_nc, op, dx_psum, HW, eps, act, slope, amax);
+    });
 }
 
 extern "C" int pcgan_instnorm_bwd(const void* dy, const void* x, const void* y, const float* mean_nc,
@@ -919,15 +914,13 @@ extern "C" int pcgan_instnorm_bwd(const void* dy, const void* x, const void* y, 
 }
 
 template <typename T>
-static void launch_bn_fwd(bool v4, hipStream_t st, const void* x, const float* gamma, const float* beta, const void* residual, void* y,
+static void launch_bn_fwd(hipStream_t st, const void* x, const float* gamma, const float* beta, const void* residual, void* y,
                           float* mean_c, float* var_c, float* running_mean, float* running_var, long long* batches, int N, int C, int HW,
                           float momentum, float eps, int act, float slope, float* y_cmax) {
-    if (v4)
-        hipLaunchKernelGGL((bn_fwd_fused_kernel<4, T>), dim3(C), dim3(256), 0, st, (const T*)x, gamma, beta, (const T*)residual, (T*)y, mean_c,
-                           var_c, running_mean, running_var, batches, N, C, HW, momentum, eps, act, slope, y_cmax);
-    else
-        hipLaunchKernelGGL((bn_fwd_fused_kernel<1, T>), dim3(C), dim3(256), 0, st, (const T*)x, gamma, beta, (const T*)residual, (T*)y, mean_c,
-                           var_c, running_mean, running_var, batches, N, C, HW, momentum, eps, act, slope, y_cmax);
+    bn_fused_dispatch(HW, [&](auto v) {
+        hipLaunchKernelGGL((bn_fwd_fused_kernel<decltype(v)::value, T>), dim3(C), dim3(256), 0, st, (const T*)x, gamma, beta, (const T*)residual, (T*)y,
+                           mean_c, var_c, running_mean, running_var, batches, N, C, HW, momentum, eps, act, slope, y_cmax);
+    });
 }
 
 extern "C" int pcgan_bn_fwd_fused(const void* x, const float* gamma, const float* beta, const void* residual, void* y,
@@ -935,22 +928,20 @@ extern "C" int pcgan_bn_fwd_fused(const void* x, const float* gamma, const float
                                   float* y_cmax, int N, int C, int HW, float momentum, float eps, int act, float slope, int dtype,
                                   pcgan_stream_t s) {
     PCGAN_CHECK(x && y && mean_c && var_c && N > 0 && C > 0 && HW > 0 && (long long)N * HW > 1, "bn_fwd_fused: bad arguments");
-    PCGAN_DTYPE_SWITCH(dtype, T, launch_bn_fwd<T>((HW & 3) == 0, (hipStream_t)s, x, gamma, beta, residual, y, mean_c, var_c, running_mean,
+    PCGAN_DTYPE_SWITCH(dtype, T, launch_bn_fwd<T>((hipStream_t)s, x, gamma, beta, residual, y, mean_c, var_c, running_mean,
                                                   running_var, batches, N, C, HW, momentum, eps, act, slope, y_cmax));
     PCGAN_LAUNCH_CHECK();
     return 0;
 }
 
 template <typename T>
-static void launch_bn_bwd(bool v4, hipStream_t st, const void* dy, const void* x, const void* y, const float* mean_c, const float* var_c,
+static void launch_bn_bwd(hipStream_t st, const void* dy, const void* x, const void* y, const float* mean_c, const float* var_c,
                           const float* gamma, void* dx, void* dres, float* s1_c, float* s2_c, int N, int C, int HW, float eps, int act, float slope,
                           float* dx_cmax) {
-    if (v4)
-        hipLaunchKernelGGL((bn_bwd_fused_kernel<4, T>), dim3(C), dim3(256), 0, st, (const T*)dy, (const T*)x, (const T*)y, mean_c, var_c, gamma,
-                           (T*)dx, (T*)dres, s1_c, s2_c, N, C, HW, eps, act, slope, dx_cmax);
-    else
-        hipLaunchKernelGGL((bn_bwd_fused_kernel<1, T>), dim3(C), dim3(256), 0, st, (const T*)dy, (const T*)x, (const T*)y, mean_c, var_c, gamma,
-                           (T*)dx, (T*)dres, s1_c, s2_c, N, C, HW, eps, act, slope, dx_cmax);
+    bn_fused_dispatch(HW, [&](auto v) {
+        hipLaunchKernelGGL((bn_bwd_fused_kernel<decltype(v)::value, T>), dim3(C), dim3(256), 0, st, (const T*)dy, (const T*)x, (const T*)y, mean_c, var_c,
+                           gamma, (T*)dx, (T*)dres, s1_c, s2_c, N, C, HW, eps, act, slope, dx_cmax);
+    });
 }
 
 extern "C" int pcgan_bn_bwd_fused(const void* dy, const void* x, const void* y, const float* mean_c, const float* var_c,
@@ -958,7 +949,7 @@ extern "C" int pcgan_bn_bwd_fused(const void* dy, const void* x, const void* y, 
                                   float eps, int act, float slope, int dtype, pcgan_stream_t s) {
     PCGAN_CHECK(dy && x && mean_c && var_c && s1_c && s2_c && N > 0 && C > 0 && HW > 0, "bn_bwd_fused: bad arguments");
     PCGAN_CHECK(act == PCGAN_ACT_NONE || y, "bn_bwd_fused: activation mask needs y");
-    PCGAN_DTYPE_SWITCH(dtype, T, launch_bn_bwd<T>((HW & 3) == 0, (hipStream_t)s, dy, x, y, mean_c, var_c, gamma, dx, dres, s1_c, s2_c, N, C, HW,
+    PCGAN_DTYPE_SWITCH(dtype, T, launch_bn_bwd<T>((hipStream_t)s, dy, x, y, mean_c, var_c, gamma, dx, dres, s1_c, s2_c, N, C, HW,
                                                   eps, act, slope, dx_cmax));
     PCGAN_LAUNCH_CHECK();
     return 0;

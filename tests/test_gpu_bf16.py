@@ -106,7 +106,9 @@ def test_residual_conv_bf16_route(Nb, H, dev):
     assert_close(dw4, w8.grad, 1e-4, 'bf16 route weight gradient (4 images)')
 
 
-@pytest.mark.parametrize('shape', [(2, 8, 32, 32), (3, 5, 7, 7), (2, 4, 128, 128), (2, 6, 15, 15)])
+@pytest.mark.parametrize('shape', [(2, 8, 32, 32), (3, 5, 7, 7), (2, 4, 128, 128), (2, 6, 15, 15),
+                                   # the tier edges of test_gpu_ops.py::test_instance_norm_fused
+                                   (2, 3, 16, 24), (1, 2, 30, 40), (1, 2, 72, 72), (1, 1, 160, 160), (2, 512, 16, 24)])
 @pytest.mark.parametrize('act,res', [(0, False), (1, False), (0, True)])
 def test_instance_norm_bf16(shape, act, res, dev):
     from pcgan_amd.hip import ops

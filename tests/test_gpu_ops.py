@@ -233,7 +233,10 @@ def test_instance_norm(shape, act, slope, res, dev):
 @pytest.mark.parametrize('shape', [(2, 8, 32, 32), (3, 5, 7, 7), (2, 4, 128, 128), (1, 2, 256, 256), (2, 6, 15, 15),
                                    (2, 3, 64, 64), (2, 3, 8, 8), (2, 16, 32, 32), (1, 32, 12, 20),
                                    # >= 1024 small planes: the wave-per-plane kernels (a plane count that is no multiple of 4, a ragged last float4 row)
-                                   (8, 128, 32, 32), (13, 79, 8, 8), (4, 256, 12, 20), (4, 272, 16, 16)])
+                                   (8, 128, 32, 32), (13, 79, 8, 8), (4, 256, 12, 20), (4, 272, 16, 16),
+                                   # edges of the body both forms share: the 128-thread tier; a ragged last round at 256 threads x 4, 1024 x 4 and
+                                   # 1024 x 16 float4 (there rounds 7 to 15 are empty in every thread); the wave form with its second round half full
+                                   (2, 3, 16, 24), (1, 2, 30, 40), (1, 2, 72, 72), (1, 1, 160, 160), (2, 512, 16, 24)])
 @pytest.mark.parametrize('act,res', [(0, False), (1, False), (0, True)])
 def test_instance_norm_fused(shape, act, res, dev):
     """register-resident single-pass kernels (and their two-pass fallback for planes that are not a multiple of 4)"""
