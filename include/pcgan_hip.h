@@ -599,6 +599,24 @@ int pcgan_proj_head_bwd(const void* g, const float* h, const float* y, const flo
                         size_t workspace_bytes, int B, int C, int HW, int nz, int By, int sigmoid, int accumulate, int dtype,
                         pcgan_stream_t s);
 
+/* ---- U-Net skip join (csrc/unet_join.hip) -----------------------------------------------------------------------------------------------
+ * UnetSkipConnectionBlock.forward, models/networks.py:729-733: `torch.cat([x, self.model(x)], 1)`, with the ReLU that the parent block
+ * applies in place to the whole concatenation (uprelu, models/networks.py:698) optionally folded into either half, and autograd's
+ * backward through both.  a[N][Ca][HW], b[N][Cb][HW], out[N][Ca + Cb][HW] and their gradients are activation tensors of `dtype`
+ * (PCGAN_F32 or PCGAN_BF16), NCHW contiguous; act_a / act_b are PCGAN_ACT_NONE or PCGAN_ACT_RELU (anything else is refused).
+ *   pcgan_skip_join_fwd   out[n][0..Ca) = act_a(a[n]),  out[n][Ca..Ca+Cb) = act_b(b[n])
+ *   pcgan_skip_join_bwd   da[n] = dout[n][0..Ca)   where a[n] > 0 under PCGAN_ACT_RELU (+0 elsewhere), everywhere under PCGAN_ACT_NONE;
+ *                         db[n] = dout[n][Ca..Ca+Cb) likewise with b.  da or db may be NULL (not wanted), not both; a (b) is read only
+ *                         when da (db) is wanted through a ReLU and may be NULL otherwise.
+ * out, da and db are fresh buffers of the caller: no output may alias an input.  Every output element is a copy of one input element or
+ * zero, so results are bit-exact in both storage types.  One launch per call: a grid-stride loop over out / dout, 16-byte accesses when
+ * Ca * HW and Cb * HW are multiples of 4 (fp32) or 8 (bf16) elements and every pointer is 16-byte aligned, element accesses otherwise;
+ * no LDS, no atomics, no workspace.  N, Ca, Cb, HW >= 1. */
+int pcgan_skip_join_fwd(const void* a, const void* b, void* out, int N, int Ca, int Cb, int HW, int act_a, int act_b, int dtype,
+                        pcgan_stream_t s);
+int pcgan_skip_join_bwd(const void* dout, const void* a, const void* b, void* da, void* db, int N, int Ca, int Cb, int HW, int act_a,
+                        int act_b, int dtype, pcgan_stream_t s);
+
 /* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),

@@ -399,6 +399,30 @@ def concat_z(img, z):
     return _ConcatZFn.apply(img, z)
 
 
+class _SkipJoinFn(torch.autograd.Function):
+    """torch.cat((act_a(a), act_b(b)), 1) as one launch per pass (ops.skip_join_fwd / skip_join_bwd); an input is saved only for a ReLU"""
+
+    @staticmethod
+    def forward(ctx, a, b, act_a, act_b):
+        a, b = _c(a), _c(b)
+        ctx.cfg = (a.shape[1], act_a, act_b)
+        ctx.save_for_backward(a if act_a != ACT_NONE else None, b if act_b != ACT_NONE else None)
+        return ops.skip_join_fwd(a, b, act_a, act_b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, b = ctx.saved_tensors
+        Ca, act_a, act_b = ctx.cfg
+        da, db = ops.skip_join_bwd(_c(dout), a, b, Ca, act_a, act_b, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return da, db, None, None
+
+
+def skip_join(a, b, act_a=ACT_NONE, act_b=ACT_NONE):
+    """The U-Net skip connection (reference models/networks.py:729-733): torch.cat((a, b), 1) with the parent block's ReLU optionally
+    folded into either half (act_a / act_b: ACT_NONE or ACT_RELU)."""
+    return _SkipJoinFn.apply(a, b, act_a, act_b)
+
+
 class _ChannelScaleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask_nc, scale):

@@ -1051,6 +1051,52 @@ def concat_z(img, z):
     return out
 
 
+def _join_acts(what, act_a, act_b):
+    for act in (act_a, act_b):
+        if act not in (ACT_NONE, _L.ACT_RELU):
+            raise RuntimeError('pcgan_amd: %s folds ACT_NONE or ACT_RELU into a half, got activation code %r' % (what, act))
+
+
+def skip_join_fwd(a, b, act_a=ACT_NONE, act_b=ACT_NONE):
+    """cat((act_a(a), act_b(b)), 1) of two (N, C, H, W) activation tensors in a fresh tensor (the U-Net skip join, csrc/unet_join.hip); it
+    carries no operand maxima: the consuming convolution takes its own absmax pass"""
+    dt = _act(a, b)
+    _join_acts('skip_join_fwd', act_a, act_b)
+    if a.dim() != 4 or b.dim() != 4 or a.shape[0] != b.shape[0] or a.shape[2:] != b.shape[2:]:
+        raise RuntimeError('pcgan_amd: skip_join_fwd joins (N, Ca, H, W) with (N, Cb, H, W), got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    N, Ca, H, W = a.shape
+    Cb = b.shape[1]
+    out = torch.empty((N, Ca + Cb, H, W), dtype=a.dtype, device=a.device)
+    if out.numel() == 0:
+        return out
+    _L.check(_L.load().pcgan_skip_join_fwd(_p(a), _p(b), _p(out), N, Ca, Cb, H * W, act_a, act_b, dt, _stream()), 'skip_join_fwd')
+    return out
+
+
+def skip_join_bwd(dout, a, b, Ca, act_a=ACT_NONE, act_b=ACT_NONE, want_a=True, want_b=True):
+    """(da, db) of skip_join_fwd for dout (N, Ca + Cb, H, W): the two channel slices of dout, zeroed where the half's input was <= 0
+    under ACT_RELU.  a / b are needed (and read) only for a wanted half under ACT_RELU; a half that is not wanted comes back None."""
+    _join_acts('skip_join_bwd', act_a, act_b)
+    need_a, need_b = want_a and act_a != ACT_NONE, want_b and act_b != ACT_NONE
+    dt = _act(dout, a if need_a else None, b if need_b else None)
+    if dout.dim() != 4 or not 0 < Ca < dout.shape[1]:
+        raise RuntimeError('pcgan_amd: skip_join_bwd splits (N, Ca + Cb, H, W) at Ca, got %s and Ca = %r' % (tuple(dout.shape), Ca))
+    N, Ct, H, W = dout.shape
+    Cb = Ct - Ca
+    for t, C, need, name in ((a, Ca, need_a, 'a'), (b, Cb, need_b, 'b')):
+        if need and (t is None or tuple(t.shape) != (N, C, H, W)):
+            raise RuntimeError('pcgan_amd: skip_join_bwd needs %s of shape %s for its ReLU mask' % (name, (N, C, H, W)))
+    if not (want_a or want_b):
+        return None, None
+    da = torch.empty((N, Ca, H, W), dtype=dout.dtype, device=dout.device) if want_a else None
+    db = torch.empty((N, Cb, H, W), dtype=dout.dtype, device=dout.device) if want_b else None
+    if dout.numel() == 0:
+        return da, db
+    _L.check(_L.load().pcgan_skip_join_bwd(_p(dout), _p(a if need_a else None), _p(b if need_b else None), _p(da), _p(db), N, Ca, Cb, H * W,
+                                           act_a, act_b, dt, _stream()), 'skip_join_bwd')
+    return da, db
+
+
 def channel_scale(x, mask_nc, scale_):
     _chk(mask_nc)
     dt = _act(x)

@@ -107,7 +107,7 @@ def init_net(net, init_type='normal', gpu_ids=[]):
 def define_G(input_nc, output_nc, nz, ngf, which_model_netG='unet_128', norm='batch', nl='relu',
              dropout=0, init_type='xavier', gpu_ids=[], upsample='bilinear', size=512, embed_size=256, n_layers_G=7):
     """reference models/networks.py:106-143.  `resnet_<n>blocks` for any n (the reference names
-    only 6 and 9; BASELINE config 1 needs 2)."""
+    only 6 and 9; BASELINE config 1 needs 2); `unet` (n_layers_G downsamplings, >= 5) and `unet_256` (8)."""
     norm_layer = get_norm_layer(norm_type=norm)
     if which_model_netG.startswith('resnet_') and which_model_netG.endswith('blocks'):
         try:
@@ -115,10 +115,19 @@ def define_G(input_nc, output_nc, nz, ngf, which_model_netG='unet_128', norm='ba
         except ValueError:
             raise NotImplementedError('Generator model name [%s] is not recognized' % which_model_netG)
         netG = ResnetGenerator(input_nc, output_nc, nz, ngf, norm_layer=norm_layer, dropout=dropout, n_blocks=n_blocks)
-    elif which_model_netG in ('unet_128', 'unet_256', 'unet_128_input', 'unet_128_all', 'unet_256_input',
-                              'unet_256_all', 'gan_stability', 'mnist_fc', 'unet', 'unet_all'):
+    elif which_model_netG == 'unet':
+        if n_layers_G < 5:
+            raise ValueError('Generator [unet] needs --n_layers_G >= 5 (the four widening blocks and the bottleneck), got %r' % (n_layers_G,))
+        netG = UnetGenerator(input_nc, output_nc, nz, n_layers_G, ngf, norm_layer=norm_layer, dropout=dropout)
+    elif which_model_netG == 'unet_256':
+        netG = UnetGenerator(input_nc, output_nc, nz, 8, ngf, norm_layer=norm_layer, dropout=dropout)
+    elif which_model_netG == 'unet_128':
+        raise NotImplementedError('Generator [unet_128] is not a name of the MI355X hot path; use --which_model_netG unet --n_layers_G 7, '
+                                  'the same network (7 downsamplings: 128 x 128 -> 1 x 1)')
+    elif which_model_netG in ('unet_128_input', 'unet_128_all', 'unet_256_input', 'unet_256_all', 'gan_stability', 'mnist_fc',
+                              'unet_all'):
         raise NotImplementedError('Generator [%s] is outside the MI355X hot path (SURVEY.md section 8); '
-                                  'use resnet_<n>blocks' % which_model_netG)
+                                  'use resnet_<n>blocks, unet or unet_256' % which_model_netG)
     else:
         raise NotImplementedError('Generator model name [%s] is not recognized' % which_model_netG)
     return init_net(netG, init_type, gpu_ids)
@@ -300,6 +309,99 @@ class ResnetBlock(tnn.Module):
             if pl is not None:
                 return HF.resblock(x, cb[1], cb[5], cb[2], cb[6], pl)
         return run_sequential(self.conv_block, x, residual=x)
+
+
+class UnetGenerator(tnn.Module):
+    """reference models/networks.py:659-677: z broadcast over the image and concatenated, then `num_downs` nested
+    UnetSkipConnectionBlocks -- from the inside out: the bottleneck (ngf*8 -> ngf*8), num_downs - 5 more of that width, ngf*4, ngf*2, ngf,
+    and the outermost block (output_nc, ngf) reading input_nc + nz channels.  state_dict keys model.model.0.weight,
+    model.model.1.model.1.weight, ... as there.  The input side must be a positive multiple of 2**num_downs (a 1 x 1 bottleneck at
+    exactly that side)."""
+
+    def __init__(self, input_nc, output_nc, nz=0, num_downs=7, ngf=64, norm_layer=hnn.BatchNorm2d, dropout=0):
+        super().__init__()
+        if dropout > 0:
+            raise NotImplementedError('pcgan_amd: generator nn.Dropout (--dropout > 0) is outside the hot path')
+        if num_downs < 5:
+            raise ValueError('pcgan_amd: UnetGenerator needs num_downs >= 5, got %r' % (num_downs,))
+        self.input_nc, self.output_nc, self.ngf, self.nz, self.num_downs = input_nc + nz, output_nc, ngf, nz, num_downs
+        block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, norm_layer=norm_layer, innermost=True)
+        for _ in range(num_downs - 5):
+            block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, submodule=block, norm_layer=norm_layer, dropout=dropout)
+        for mult in (4, 2, 1):
+            block = UnetSkipConnectionBlock(ngf * mult, ngf * mult * 2, submodule=block, norm_layer=norm_layer)
+        self.model = UnetSkipConnectionBlock(output_nc, ngf, input_nc=input_nc + nz, submodule=block, outermost=True, norm_layer=norm_layer)
+
+    def forward(self, input, z=None):
+        side = 1 << self.num_downs
+        for s in (input.shape[2], input.shape[3]):
+            if s < side or s % side != 0:
+                raise ValueError('pcgan_amd: UnetGenerator input side %d is not a positive multiple of %d = 2**num_downs (num_downs = %d)'
+                                 % (s, side, self.num_downs))
+        return self.model(HF.concat_z(input, z) if z is not None else input)
+
+
+def _norm_then_act(norm, x, act=hnn.ACT_NONE, slope=0.0):
+    """norm(x) with the following activation inside the normalisation pass; norm 'none' (IdentityMapping) leaves the activation alone"""
+    if isinstance(norm, (hnn.InstanceNorm2d, hnn.BatchNorm2d)):
+        return norm(x, act, slope)
+    return HF.activation(norm(x), act, slope)
+
+
+class UnetSkipConnectionBlock(tnn.Module):
+    """reference models/networks.py:683-733.  Sequential layouts (the indices are the state_dict keys):
+      outermost  [0]Conv4s2 [1]sub [2]ReLU [3]ConvT4s2 (bias always) [4]Tanh
+      middle     [0]LeakyReLU(0.2) [1]Conv4s2 [2]norm [3]sub [4]ReLU [5]ConvT4s2 [6]norm
+      innermost  [0]LeakyReLU(0.2) [1]Conv4s2 [2]ReLU [3]ConvT4s2 [4]norm
+    A block that is not the outermost returns cat(t, up(down(t))) with t = LeakyReLU(x): the reference's first module rewrites x in
+    place, so the skip carries t, not x.  Its parent's ReLU then acts on that whole concatenation.  Here every activation runs inside
+    the kernel that produces its operand -- LeakyReLU in the epilogue of the convolution or normalisation above it, ReLU in the
+    up-normalisation and, for the skip half, in the join (HF.skip_join) -- so t is written once and read by the down-convolution and
+    by the join."""
+
+    def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False,
+                 norm_layer=hnn.BatchNorm2d, dropout=0):
+        super().__init__()
+        if dropout > 0:
+            raise NotImplementedError('pcgan_amd: generator nn.Dropout (--dropout > 0) is outside the hot path')
+        if outermost and innermost:
+            raise ValueError('pcgan_amd: a UnetSkipConnectionBlock is outermost or innermost, not both')
+        if (submodule is None) != bool(innermost):
+            raise ValueError('pcgan_amd: exactly the innermost UnetSkipConnectionBlock has no submodule')
+        self.outermost, self.innermost = outermost, innermost
+        use_bias = _is_instance_norm(norm_layer)
+        down = hnn.Conv2d(outer_nc if input_nc is None else input_nc, inner_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+        up_in = inner_nc if innermost else inner_nc * 2
+        up = hnn.ConvTranspose2d(up_in, outer_nc, kernel_size=4, stride=2, padding=1, bias=use_bias or outermost)
+        # (down before up, as in the reference: a convolution's default initialisation draws from torch's generator; norms draw nothing)
+        if outermost:
+            seq = [down, submodule, tnn.ReLU(True), up, tnn.Tanh()]
+        elif innermost:
+            seq = [tnn.LeakyReLU(0.2, True), down, tnn.ReLU(True), up, norm_layer(outer_nc)]
+        else:
+            seq = [tnn.LeakyReLU(0.2, True), down, norm_layer(inner_nc), submodule, tnn.ReLU(True), up, norm_layer(outer_nc)]
+        self.model = tnn.Sequential(*seq)
+
+    def forward(self, x):
+        m = self.model
+        if self.outermost:
+            t = m[0](x, 0, 0, hnn.ACT_LRELU, m[1].model[0].negative_slope)      # the sub-block's LeakyReLU in this epilogue
+            return HF.activation(m[3](m[1].joined(t, True)), hnn.ACT_TANH)
+        return self.joined(HF.activation(x, hnn.ACT_LRELU, m[0].negative_slope), False)
+
+    def joined(self, t, relu):
+        """cat(t, up(down(t))) for t = LeakyReLU(x) already applied by the producer of t; relu: the parent's ReLU folded in (into the
+        up-normalisation for the new half, into the join for the skip half)"""
+        m = self.model
+        act = hnn.ACT_RELU if relu else hnn.ACT_NONE
+        if self.innermost:
+            u = m[1](t, 0, 0, hnn.ACT_RELU)
+            y = _norm_then_act(m[4], m[3](u), act)
+        else:
+            sub = m[3]
+            d = _norm_then_act(m[2], m[1](t), hnn.ACT_LRELU, sub.model[0].negative_slope)
+            y = _norm_then_act(m[6], m[5](sub.joined(d, True)), act)
+        return HF.skip_join(t, y, act, hnn.ACT_NONE)
 
 
 # ------------------------------------------------------------------------- discriminator

@@ -3,8 +3,9 @@ HIP path: G(image, attribute) with an unconditional PatchGAN, an AlexNet identit
 here (it regresses the attribute back: x -> y -> x and y -> x -> y cycles).  SURVEY.md 8(f) rank 1 / config 5.
 
 Same plugin surface as the reference (flags, defaults, loss / visual / model names, step order: D first, then G and E
-together).  Differences, all stated where they occur: generators outside the hot path (the reference's default
-`unet_128`) raise NotImplementedError from define_G -- pass `--which_model_netG resnet_9blocks`; `--use_bicycle_E`
+together).  Differences, all stated where they occur: the reference's default generator name `unet_128` raises
+NotImplementedError from define_G -- pass `--which_model_netG unet` (the same U-Net: like the reference, this model does not
+hand `--n_layers_G` on, so its `unet` always has the default 7 downsamplings), `unet_256` or `resnet_9blocks`; the BicycleGAN U-Nets (`unet_*_input`, `unet_*_all`) are outside the hot path; `--use_bicycle_E`
 (another encoder family) raises; data parallelism is one process per GPU + RCCL all-reduce of the three flat
 gradient buffers instead of nn.DataParallel.
 """

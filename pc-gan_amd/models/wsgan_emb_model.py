@@ -108,6 +108,8 @@ _TRAIN_FLAGS = [
     ('--detach_fake_B', dict(action='store_true')),
     ('--update_logvar_E', dict(type=str2bool, default=False)),
 ]
+# (the reference's defaults, kept: define_G refuses the NAME `unet_128` and names `--which_model_netG unet`, which with the default
+# `--n_layers_G 7` is that network)
 _DEFAULT_OVERRIDES = dict(pool_size=0, no_lsgan=True, norm='instance', dataset_mode='wsgan_emb',
                           which_model_netG='unet_128', which_model_netD='n_layers', n_layers_D=4, batchSize=10,
                           loadSize=128, fineSize=128, display_visuals=True, save_epoch_freq=2)
