@@ -645,6 +645,10 @@ int pcgan_set_nonfinite_counter(unsigned int* dev_word);
  *   "hgemm_tile"    0  packed implicit GEMM, layers with > 32 output rows: 0 = the library's tile heuristic; BM * 1000 + BP with
  *                      BM, BP in {64, 128} forces the workgroup tile (measurement: scripts/sweep_hgemm.py)
  *   "hgemm_ks"      0  ... and the K split: 0 = heuristic, 1 .. 8 forced (every layer's workspace query then includes the partial sums)
+ *   "wgrad_ks"      0  pcgan_conv2d_bwd_weight: 0 = the library's split heuristic; 1 .. 512 forces that many pixel (strip) splits for
+ *                      every kernel family, cut to [1, chunks of 32 pixels (strips)] and not held to the heuristic's 8-chunk floor; the
+ *                      chunks of a split and the final count are re-derived as always, and the workspace query follows (tests:
+ *                      tests/test_gpu_wgrad_generic.py; the host maps no environment variable onto it)
  * Unknown keys / values return non-zero. */
 int pcgan_set_option(const char* key, int value);
 int pcgan_get_option(const char* key, int* value);
@@ -663,6 +667,18 @@ int pcgan_timer_read(int kind, float* ms, int cap);
 #define PCGAN_IGEMM_GENERIC 5      /* igemm_kernel, generic K order */
 #define PCGAN_IGEMM_SMALLM 6       /* <= 4 output channels, vector ALU */
 int pcgan_igemm_last_launch(int* info, int n);
+/* Launch record of pcgan_conv2d_bwd_weight (host memory, no synchronisation; a record of its own: the one above does not move when a weight
+ * gradient runs): which instantiation its last call launched, after every clamp of a forced "wgrad_ks".  info[0 .. n) = {sequence number
+ * (+1 per recorded launch), family (PCGAN_WGRAD_*), padding mode (0 zero, 1 reflection), BM (0 for the small-M kernels), VECA (dY fetched
+ * four pixels at a time; tile kernels only), variant (see the families), storage type (PCGAN_F32 / PCGAN_BF16), splits, units per split
+ * (chunks of 32 pixels; strips for PCGAN_WGRAD_STRIP)}; entries past PCGAN_WGRAD_LAUNCH_INFO are 0.  The hsplit / bsplit / row-ring /
+ * direct weight gradients do not record. */
+#define PCGAN_WGRAD_LAUNCH_INFO 9
+#define PCGAN_WGRAD_TILE2 1   /* wgrad2_kernel (tap-aligned K tiles, pipelined); variant = taps per K tile, 2 | 1 */
+#define PCGAN_WGRAD_TILE 2    /* wgrad_kernel; variant = KMODE 0 (generic) | 1 (per-thread tap) | 2 (one tap per K tile) */
+#define PCGAN_WGRAD_SMALLM 3  /* smallm_wgrad_kernel (<= 4 output channels, multiple of 16 padded channels); variant 0 */
+#define PCGAN_WGRAD_STRIP 4   /* smallm_wgrad_strip_kernel (<= 3 output channels, stride 1); variant = NT 4 | 7 */
+int pcgan_wgrad_last_launch(int* info, int n);
 
 #ifdef __cplusplus
 }

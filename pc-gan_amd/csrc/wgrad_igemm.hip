@@ -1,6 +1,7 @@
 // Weight gradient of the implicit-GEMM convolution: Wp[split][m][k] = sum over a pixel range of dY[m][pix] * G(k; pix), then a
 // deterministic second-pass sum over the splits (wgrad_reduce_kernel, no atomics).  Shared gathers and argument structs: igemm.h.
 #include "igemm.h"
+#include <mutex>
 
 namespace pcgan {
 
@@ -698,6 +699,12 @@ static inline bool smallm_wgrad_strip(const pcgan_conv_desc* d) {
     return d->K <= 3 && d->stride == 1 && d->R <= 7 && d->S <= 7 && d->R >= 3 && d->P >= 16 && d->C >= 16;
 }
 
+// option "wgrad_ks" > 0 (tests): that many splits for every family, cut to [1, units]; the callers re-derive the units of a split
+static inline int forced_splits(int units) {
+    const int fk = option(OPT_WGRAD_KS);
+    return fk <= 0 ? 0 : (fk > units ? (units > 0 ? units : 1) : fk);
+}
+
 int wgrad_splits(const pcgan_conv_desc* d, int* chunks_per_split) {
     const int Cgp = round4(d->C);
     if (smallm_wgrad_strip(d)) {   // one workgroup per input channel and strip range; ~2048 workgroups, >= 4 strips per thread
@@ -705,6 +712,7 @@ int wgrad_splits(const pcgan_conv_desc* d, int* chunks_per_split) {
         int splits = 1024 / d->C;
         if (splits > nstrips / 1024) splits = nstrips / 1024;
         if (splits < 1) splits = 1;
+        if (const int fk = forced_splits(nstrips)) splits = fk;
         const int sps = (nstrips + splits - 1) / splits;
         *chunks_per_split = sps;
         return (nstrips + sps - 1) / sps;
@@ -715,6 +723,7 @@ int wgrad_splits(const pcgan_conv_desc* d, int* chunks_per_split) {
         int splits = 2048 / (Kp / 16);
         if (splits > chunks / 64) splits = chunks / 64;  // >= 8 pixels per thread
         if (splits < 1) splits = 1;
+        if (const int fk = forced_splits(chunks)) splits = fk;
         int cps = (chunks + splits - 1) / splits;
         *chunks_per_split = cps;
         return (chunks + cps - 1) / cps;
@@ -751,6 +760,7 @@ int wgrad_splits(const pcgan_conv_desc* d, int* chunks_per_split) {
     if (splits > chunks / 8) splits = chunks / 8;  // at least 8 stages of work per block
     if (splits < 1) splits = 1;
     if (splits > 512) splits = 512;
+    if (const int fk = forced_splits(chunks)) splits = fk;   // (not subject to the 8-stage floor)
     int cps = (chunks + splits - 1) / splits;
     splits = (chunks + cps - 1) / cps;
     *chunks_per_split = cps;
@@ -760,48 +770,67 @@ int wgrad_splits(const pcgan_conv_desc* d, int* chunks_per_split) {
 // kernel choice -- 2 modes (zero / reflection padding) x 2 storage types of:
 //   smallm_wgrad_strip_kernel<MODE, NT = 4 | 7>, smallm_wgrad_kernel<MODE>,
 //   wgrad2_kernel<MODE, BM = 128 | 64 | 32, VECA, NT = 2 | 1>, wgrad_kernel<MODE, BM = 128 | 64 | 32, KMODE = 0 | 1 | 2, VECA>
+// (which: {family PCGAN_WGRAD_*, BM, VECA, variant} of the instantiation launched, for the launch record)
 template <int MODE, int BM, bool VECA>
-static void launch_tile(const pcgan_conv_desc* d, const WgradArgs& a, dim3 grid, hipStream_t st) {
+static void launch_tile(const pcgan_conv_desc* d, const WgradArgs& a, dim3 grid, hipStream_t st, int* which) {
     const int Cgp = a.Cgp;
+    which[0] = PCGAN_WGRAD_TILE; which[1] = BM; which[2] = VECA;
     if ((d->C % 64) == 0 && ((Cgp % 128) == 0 || Cgp == 64)) {
+        which[0] = PCGAN_WGRAD_TILE2; which[3] = Cgp == 64 ? 2 : 1;
         if (Cgp == 64) LAUNCH_TA(a.dtype, wgrad2_kernel, grid, a, MODE, BM, VECA, 2);
         else LAUNCH_TA(a.dtype, wgrad2_kernel, grid, a, MODE, BM, VECA, 1);
     } else if ((Cgp % 8) != 0) {
+        which[3] = 1;
         LAUNCH_TA(a.dtype, wgrad_kernel, grid, a, MODE, BM, 1, VECA);
     } else if ((Cgp % 128) == 0) {
+        which[3] = 2;
         LAUNCH_TA(a.dtype, wgrad_kernel, grid, a, MODE, BM, 2, VECA);
     } else {
+        which[3] = 0;
         LAUNCH_TA(a.dtype, wgrad_kernel, grid, a, MODE, BM, 0, VECA);
     }
 }
 template <int MODE>
-static void launch_mode(const pcgan_conv_desc* d, const WgradArgs& a, int splits, hipStream_t st) {
+static void launch_mode(const pcgan_conv_desc* d, const WgradArgs& a, int splits, hipStream_t st, int* which) {
     if (smallm_wgrad_strip(d)) {
         const bool nt4 = d->R <= 4 && d->S <= 4;
         const dim3 sgrid((unsigned)d->C, (unsigned)splits, (unsigned)(nt4 ? 1 : (d->S + 3) / 4));
+        which[0] = PCGAN_WGRAD_STRIP; which[3] = nt4 ? 4 : 7;
         if (nt4) LAUNCH_TA(a.dtype, smallm_wgrad_strip_kernel, sgrid, a, MODE, 4);
         else LAUNCH_TA(a.dtype, smallm_wgrad_strip_kernel, sgrid, a, MODE, 7);
         return;
     }
     if (smallm_wgrad(d)) {
         const dim3 sgrid((unsigned)(a.Kp / 16), (unsigned)splits);
+        which[0] = PCGAN_WGRAD_SMALLM;
         LAUNCH_TA(a.dtype, smallm_wgrad_kernel, sgrid, a, MODE);
         return;
     }
     const int bm = a.M > 64 ? 128 : (a.M > 32 ? 64 : 32);
     const dim3 grid((unsigned)(((a.M + bm - 1) / bm) * ((a.Kp + 127) / 128)), (unsigned)splits);
     const bool veca = ((d->P * d->Q) % 4) == 0;
-    if (bm == 128 && veca) launch_tile<MODE, 128, true>(d, a, grid, st);
-    else if (bm == 128) launch_tile<MODE, 128, false>(d, a, grid, st);
-    else if (bm == 64 && veca) launch_tile<MODE, 64, true>(d, a, grid, st);
-    else if (bm == 64) launch_tile<MODE, 64, false>(d, a, grid, st);
-    else if (veca) launch_tile<MODE, 32, true>(d, a, grid, st);
-    else launch_tile<MODE, 32, false>(d, a, grid, st);
+    if (bm == 128 && veca) launch_tile<MODE, 128, true>(d, a, grid, st, which);
+    else if (bm == 128) launch_tile<MODE, 128, false>(d, a, grid, st, which);
+    else if (bm == 64 && veca) launch_tile<MODE, 64, true>(d, a, grid, st, which);
+    else if (bm == 64) launch_tile<MODE, 64, false>(d, a, grid, st, which);
+    else if (veca) launch_tile<MODE, 32, true>(d, a, grid, st, which);
+    else launch_tile<MODE, 32, false>(d, a, grid, st, which);
 }
 
+// host-side record of the last launch launch_wgrad decided (pcgan_wgrad_last_launch): a record of its own -- the implicit GEMM's
+// (record_launch, igemm_conv.hip) does not move when a weight gradient runs
+static std::mutex g_wgrad_mu;
+static int g_wgrad_rec[PCGAN_WGRAD_LAUNCH_INFO] = {0};
+
 int launch_wgrad(const pcgan_conv_desc* d, const WgradArgs& a, int splits, float* dw, int accumulate, hipStream_t st) {
-    if (d->pad_mode == 1) launch_mode<MODE_FWD_REFLECT>(d, a, splits, st);
-    else launch_mode<MODE_FWD_ZERO>(d, a, splits, st);
+    int which[4] = {0, 0, 0, 0};
+    if (d->pad_mode == 1) launch_mode<MODE_FWD_REFLECT>(d, a, splits, st, which);
+    else launch_mode<MODE_FWD_ZERO>(d, a, splits, st, which);
+    {
+        std::lock_guard<std::mutex> lk(g_wgrad_mu);
+        const int v[PCGAN_WGRAD_LAUNCH_INFO] = {g_wgrad_rec[0] + 1, which[0], d->pad_mode == 1 ? 1 : 0, which[1], which[2], which[3], a.dtype, splits, a.chunks_per_split};
+        for (int i = 0; i < PCGAN_WGRAD_LAUNCH_INFO; ++i) g_wgrad_rec[i] = v[i];
+    }
     PCGAN_LAUNCH_CHECK();
     const int RS = d->R * d->S;
     const size_t total = (size_t)d->K * RS * a.Cgp;
@@ -812,3 +841,11 @@ int launch_wgrad(const pcgan_conv_desc* d, const WgradArgs& a, int splits, float
 }
 
 }  // namespace pcgan
+
+extern "C" int pcgan_wgrad_last_launch(int* info, int n) {
+    using namespace pcgan;
+    PCGAN_CHECK(info != nullptr && n > 0, "wgrad_last_launch: null output");
+    std::lock_guard<std::mutex> lk(g_wgrad_mu);
+    for (int i = 0; i < n; ++i) info[i] = i < PCGAN_WGRAD_LAUNCH_INFO ? g_wgrad_rec[i] : 0;
+    return 0;
+}

@@ -989,6 +989,20 @@ def igemm_last_launch():
     return {'seq': seq, 'form': IGEMM_FORMS.get(form), 'mode': IGEMM_MODES.get(mode), 'bm': bm, 'bp': bp, 'ks': ks, 'nphase': nph}
 
 
+WGRAD_FAMILIES = {1: 'tile2', 2: 'tile', 3: 'smallm', 4: 'strip'}
+
+
+def wgrad_last_launch():
+    """what the last pcgan_conv2d_bwd_weight launched (pcgan_wgrad_last_launch, host memory): {'seq', 'family', 'mode', 'bm', 'veca',
+    'variant', 'dtype', 'splits', 'units'} with the family as a name (tile2: variant = NT; tile: KMODE; strip: NT); units = chunks of 32
+    pixels (strips) per split; seq grows by one per recorded launch"""
+    buf = (ctypes.c_int * 9)()
+    _L.check(_L.load().pcgan_wgrad_last_launch(buf, 9), 'wgrad_last_launch')
+    seq, fam, mode, bm, veca, variant, dt, splits, units = list(buf)
+    return {'seq': seq, 'family': WGRAD_FAMILIES.get(fam), 'mode': mode, 'bm': bm, 'veca': veca, 'variant': variant, 'dtype': dt,
+            'splits': splits, 'units': units}
+
+
 # ---------------------------------------------------------------- pointwise
 def channel_sum(x, accumulate_into=None):
     _chk(accumulate_into)

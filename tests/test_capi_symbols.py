@@ -96,7 +96,7 @@ def test_library_reads_no_environment_and_options_are_explicit():
         assert 'getenv' not in open(src).read(), src
     h = lib.load()
     for key, default in (('bsplit_halo', 1), ('wgrad_gen', 1), ('wgrad_padcopy', 0), ('wgrad_cw', 0), ('hgemm_bf16', 1), ('wgrad_direct', 0),
-                         ('hgemm_tile', 0), ('hgemm_ks', 0), ('wgrad_rowring', 1)):
+                         ('hgemm_tile', 0), ('hgemm_ks', 0), ('wgrad_rowring', 1), ('wgrad_ks', 0)):
         if not any(os.environ.get(e) for e, k, _ in lib._ENV_OPTIONS if k == key):
             assert lib.get_option(key) == default, key
     lib.set_option('wgrad_cw', 256)
@@ -105,6 +105,8 @@ def test_library_reads_no_environment_and_options_are_explicit():
     assert h.pcgan_set_option(b'no_such_option', 1) != 0 and b'unknown option' in h.pcgan_last_error()
     assert h.pcgan_set_option(b'wgrad_cw', 77) != 0
     assert h.pcgan_set_option(b'hgemm_tile', 96096) != 0 and h.pcgan_set_option(b'hgemm_ks', 9) != 0
+    assert h.pcgan_set_option(b'wgrad_ks', 513) != 0 and b'wgrad_ks' in h.pcgan_last_error() and h.pcgan_set_option(b'wgrad_ks', -1) != 0
+    assert lib.get_option('wgrad_ks') == 0 and not any(k == 'wgrad_ks' for _, k, _ in lib._ENV_OPTIONS)
 
 
 def test_igemm_launch_record_query():
@@ -115,3 +117,48 @@ def test_igemm_launch_record_query():
     buf = (ctypes.c_int * 9)(*([-1] * 9))
     assert h.pcgan_igemm_last_launch(buf, 9) == 0 and list(buf)[7:] == [0, 0] and min(buf) >= 0
     assert h.pcgan_igemm_last_launch(None, 7) != 0 and b'igemm_last_launch' in h.pcgan_last_error()
+
+
+def test_wgrad_launch_record_query():
+    """pcgan_wgrad_last_launch reads host memory only (callable without a GPU): entries past the record are 0, a null output is refused,
+    and it is a record of its own -- the query leaves the implicit GEMM's where it was"""
+    import ctypes
+    from pcgan_amd.hip import lib, ops
+    h = lib.load()
+    ig = (ctypes.c_int * 7)()
+    assert h.pcgan_igemm_last_launch(ig, 7) == 0
+    buf = (ctypes.c_int * 11)(*([-1] * 11))
+    assert h.pcgan_wgrad_last_launch(buf, 11) == 0 and list(buf)[9:] == [0, 0] and min(buf) >= 0
+    assert h.pcgan_wgrad_last_launch(None, 9) != 0 and b'wgrad_last_launch' in h.pcgan_last_error()
+    assert h.pcgan_wgrad_last_launch(buf, 0) != 0
+    rec = ops.wgrad_last_launch()
+    assert sorted(rec) == ['bm', 'dtype', 'family', 'mode', 'seq', 'splits', 'units', 'variant', 'veca'] and rec['seq'] == buf[0]
+    ig2 = (ctypes.c_int * 7)()
+    assert h.pcgan_igemm_last_launch(ig2, 7) == 0 and list(ig2) == list(ig)
+
+
+def test_forced_wgrad_splits_size_the_workspace():
+    """option "wgrad_ks" (host arithmetic only): the workspace query holds exactly the forced number of partial sums, cut to the number
+    of 32-pixel chunks (strips), for the tile, small-M and strip families; 0 gives the heuristic's size back"""
+    import ctypes
+    from pcgan_amd.hip import lib
+    h = lib.load()
+
+    def nbytes(d):
+        return int(h.pcgan_conv2d_workspace_bytes(ctypes.byref(d), lib.PASS_BWD_WEIGHT))
+
+    def up(v):
+        return (v + 255) // 256 * 256
+    tile = lib.ConvDesc(1, 24, 10, 20, 8, 3, 3, 1, 1, 0, 10, 20)        # 200 pixels: 7 chunks; Kp = 9 * 24
+    smallm = lib.ConvDesc(1, 16, 10, 20, 2, 1, 1, 1, 0, 0, 10, 20)      # 7 chunks; Kp = 16
+    strip = lib.ConvDesc(2, 16, 19, 13, 3, 3, 3, 1, 1, 0, 19, 13)       # 2 * 3 * 13 = 78 strips; Kp = 9 * 16
+    before = [nbytes(d) for d in (tile, smallm, strip)]
+    try:
+        for ks, units in ((1, (1, 1, 1)), (3, (3, 3, 3)), (4, (4, 4, 4)), (5, (4, 4, 5)), (7, (7, 7, 7)), (100, (7, 7, 78)), (512, (7, 7, 78))):
+            lib.set_option('wgrad_ks', ks)      # (5 over 7 chunks: 2 chunks per split -> 4 splits; 5 over 78 strips: 16 per split -> 5)
+            assert nbytes(tile) == up(units[0] * 8 * 9 * 24 * 4), ks
+            assert nbytes(smallm) == up(units[1] * 2 * 16 * 4), ks
+            assert nbytes(strip) == up(units[2] * 3 * 9 * 16 * 4), ks
+    finally:
+        lib.set_option('wgrad_ks', 0)
+    assert [nbytes(d) for d in (tile, smallm, strip)] == before
