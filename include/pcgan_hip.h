@@ -564,6 +564,28 @@ int pcgan_linear_ce_fwd(const void* x, const float* w, const float* b, const int
 int pcgan_linear_bwd(const void* dlogits, const void* x, const float* w, void* dx, float* dw, float* db, int N, int C, int K,
                      int accumulate, int dtype, pcgan_stream_t s);
 
+/* ---- end of the attribute regressor: pooling + MSE + "within delta" accuracy + gradient (csrc/pool_mse_head.hip) ---------------------
+ * What regression.py's training iteration does after the conv head of networks.RegressionNetwork.  Replaces
+ *   output = net.forward(img0); loss = criterion(output, label); get_accuracy(output, label, opt.delta)     regression.py:359-363
+ *   nn.AvgPool2d(output.size(2))(output) / nn.MaxPool2d(output.size(2))(output)                             models/networks.py:1115-1118
+ * and the backward pass of both.  x is [N][F][HW] in fp32 or bf16 storage (dtype), target [N F] fp32.  pcgan_pool_mse_fwd, ONE launch:
+ *   pred[n][f]  = mean (is_max == 0: float64 sum in index order, divided, rounded to fp32 once) or maximum (exact) of the plane;
+ *   argmax[n][f] = index of the FIRST maximum (is_max != 0 only; the convention of pcgan_global_pool_fwd)
+ *   loss        = sum (pred - target)^2 / (N F)           differences in float64 from the fp32 pred, fixed order, rounded once
+ *   hits        = #{ |pred - target| < delta }            in fp32, as torch.abs(pred - target) < delta on the returned pred; strict
+ *   dx[n][f][i] = gscale 2 (pred - target) / (N F) (1 / HW for the mean | [i == argmax] for the maximum)
+ *                 float64, rounded to fp32 once, then to bf16 (nearest even) in bf16 storage; x's storage type, always all of it written
+ * pred, argmax, dx, loss and hits may each be NULL (not wanted); argmax must be given when is_max and dx both are.  Sizes: N, F >= 1,
+ * N F <= 2^22, 1 <= HW <= 2^20.  Planes of up to 64 elements (3x3 .. 8x8 maps, the regressor's) are handled 128 per workgroup with one
+ * lane per plane; longer ones by a workgroup each.  x / dx aligned to four elements are accessed four elements at a time, otherwise
+ * element by element -- the same values either way.  No float atomics: results are bit-identical from run to run.
+ * workspace: pcgan_pool_mse_workspace_bytes(N F) bytes (0: N F out of range), 8-byte aligned, caller-owned.  Its first word is the
+ * arrival ticket of the last-arriver reduction of loss / hits: it must be ZERO before the first call and is left zero by every call, so
+ * calls in stream order may share it whatever their sizes; calls on different streams need one each. */
+size_t pcgan_pool_mse_workspace_bytes(int NF);
+int pcgan_pool_mse_fwd(const void* x, const float* target, float* pred, int32_t* argmax, void* dx, float* loss, int32_t* hits, void* ws,
+                       size_t ws_bytes, int N, int F, int HW, int is_max, float delta, float gscale, int dtype, pcgan_stream_t s);
+
 /* ---- head of the projection discriminator (csrc/proj_head.hip) -------------------------------------------------------------------------
  * NLayerProjectionDiscriminator.forward with proj=True ("cGANs with Projection Discriminator").  Replaces
  *   h = torch.sum(self.phi(input), dim=(2, 3), keepdim=True)                 models/networks.py:830

@@ -645,6 +645,53 @@ def linear_cross_entropy(x, w, b, labels, class_weight=None):
     return _LinearCeFn.apply(x, w, b, labels, class_weight)
 
 
+# ---------------------------------------------------------------------------- end of the attribute regressor
+_UNIT = {}
+
+
+def unit_gradient(like):
+    """THE gradient 1 of a scalar on `like`'s device: one cached 0-dim fp32 tensor per device.  `loss.backward(unit_gradient(loss))` is
+    `loss.backward()` whose factor a node can recognise on the host (by address) without reading device memory: _PooledMseFn then hands
+    its stored gradient on as it is.  Any other incoming gradient -- the implicit ones of a bare backward() included -- is a device
+    value the host does not look at, and goes through pcgan_scale."""
+    key = like.device
+    if key not in _UNIT:
+        _UNIT[key] = torch.ones((), dtype=torch.float32, device=like.device)
+    return _UNIT[key]
+
+
+class _PooledMseFn(torch.autograd.Function):
+    """global pooling + nn.MSELoss + the "within delta" count as ONE node (pcgan_pool_mse_fwd): the forward launch leaves d loss / d x
+    behind, so backward launches nothing when the incoming factor is unit_gradient() and one pcgan_scale otherwise.  Only `loss` is
+    differentiable; pred and hits are by-products for the caller's accuracy."""
+
+    @staticmethod
+    def forward(ctx, x, target, delta, is_max):
+        x = _c(x)
+        loss, pred, hits, dx, _ = ops.pool_mse_fwd(x, _c(target), delta, is_max, 1.0, x.requires_grad)
+        ctx.save_for_backward(dx)
+        ctx.mark_non_differentiable(pred, hits)
+        ctx.set_materialize_grads(False)
+        return loss, pred, hits
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        (dx,) = ctx.saved_tensors
+        if dx is None or dloss is None:
+            return None, None, None, None
+        unit = _UNIT.get(dloss.device)
+        if unit is not None and dloss.data_ptr() == unit.data_ptr():
+            return dx, None, None, None
+        # d loss / d x, scaled by the upstream scalar which stays on the device
+        return ops.scale(dx, _c(dloss).to(torch.float32).reshape(1)), None, None, None
+
+
+def pooled_mse(x, target, delta, is_max):
+    """(loss, pred, hits) of nn.MSELoss()(pool(x), target) for x (N, F, H, W), pool = nn.MaxPool2d(H) (is_max) or nn.AvgPool2d(H):
+    pred (N, F, 1, 1) fp32, hits = #{|pred - target| < delta} (a 0-dim int32 device tensor)"""
+    return _PooledMseFn.apply(x, target, float(delta), bool(is_max))
+
+
 # ---------------------------------------------------------------------------- projection discriminator head
 class _ProjectionHeadFn(torch.autograd.Function):
     """The head of NLayerProjectionDiscriminator (reference models/networks.py:830-838) as ONE node: pcgan_proj_head_fwd leaves the plane

@@ -166,6 +166,8 @@ SIGNATURES = {
     'pcgan_proj_head_fwd': (_i, [_vp] * 8 + [_i] * 7 + [_vp]),
     'pcgan_proj_head_bwd_workspace_bytes': (_sz, [_i, _i]),
     'pcgan_proj_head_bwd': (_i, [_vp] * 14 + [_sz] + [_i] * 8 + [_vp]),
+    'pcgan_pool_mse_workspace_bytes': (_sz, [_i]),
+    'pcgan_pool_mse_fwd': (_i, [_vp] * 8 + [_sz] + [_i] * 4 + [_f, _f, _i, _vp]),
     'pcgan_skip_join_fwd': (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
     'pcgan_skip_join_bwd': (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
 }

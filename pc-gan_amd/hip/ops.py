@@ -1429,6 +1429,33 @@ def linear_bwd(dlogits, x, w, want_dx=True, want_dw=True, want_db=True, dw_into=
     return dx, dw, db
 
 
+# ---------------------------------------------------------------- end of the attribute regressor (csrc/pool_mse_head.hip)
+def pool_mse_fwd(x, target, delta, is_max, gscale=1.0, want_grad=True):
+    """(loss, pred, hits, dx, argmax) of global pooling + nn.MSELoss + the "within delta" count through pcgan_pool_mse_fwd, one launch:
+    x (N, F, H, W) in fp32 or bf16 storage, target N F fp32 values in any shape.  loss is a 0-dim fp32 tensor, pred (N, F, 1, 1) fp32,
+    hits a 0-dim int32 tensor -- all on the device, nothing is read back; dx = gscale d loss / d x in x's storage type (None unless
+    want_grad); argmax (N, F) int32, the first maximum of every plane (None for the mean)."""
+    dt = _act(x)
+    _chk(target)
+    if x.dim() != 4:
+        raise RuntimeError('pool_mse_fwd: x must be (N, F, H, W), got %s' % (tuple(x.shape),))
+    N, F, H, W = x.shape
+    if target.numel() != N * F or target.device != x.device:
+        raise RuntimeError('pool_mse_fwd: target of shape %s on %s for %d x %d pooled values on %s'
+                           % (tuple(target.shape), target.device, N, F, x.device))
+    lib = _L.load()
+    nbytes = lib.pcgan_pool_mse_workspace_bytes(N * F)
+    ws = _ce_workspace(x.device, nbytes) if nbytes else None
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    pred = torch.empty((N, F, 1, 1), dtype=torch.float32, device=x.device)
+    hits = torch.empty((), dtype=torch.int32, device=x.device)
+    dx = torch.empty_like(x) if want_grad else None
+    arg = torch.empty((N, F), dtype=torch.int32, device=x.device) if is_max else None
+    _L.check(lib.pcgan_pool_mse_fwd(_p(x), _p(target), _p(pred), _p(arg), _p(dx), _p(loss), _p(hits), _p(ws), nbytes, N, F, H * W,
+                                    int(bool(is_max)), float(delta), float(gscale), dt, _stream()), 'pool_mse_fwd')
+    return loss, pred, hits, dx, arg
+
+
 # ---------------------------------------------------------------- projection discriminator head (csrc/proj_head.hip)
 def _proj_check(what, B, C, y, psi_w, psi_b, ly_w, ly_b):
     _chk(y, psi_w, psi_b, ly_w, ly_b)

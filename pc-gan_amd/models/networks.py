@@ -2,7 +2,7 @@
 
 Same plugin surface as the reference's models/networks.py for the part of the zoo that the
 wsgan_emb / wsgan_cycle configurations reach:
-define_G / define_D / define_E / define_IP, get_norm_layer, init_weights, init_net,
+define_G / define_D / define_E / define_IP / define_AR, get_norm_layer, init_weights, init_net,
 get_scheduler, GANLoss, and the module classes with the reference's nn.Sequential index
 layout, so state_dict keys are identical (`model.10.conv_block.1.weight`, `model.2.running_mean`,
 ...).  Architectures outside that scope raise NotImplementedError naming themselves.
@@ -182,6 +182,22 @@ def define_E(which_model_netE, input_nc=3, init_type='kaiming', pooling='max', c
     netE = SiameseFeature(base, pooling=pooling, cnn_dim=cnn_dim, cnn_pad=cnn_pad, cnn_relu_slope=cnn_relu_slope,
                           noisy=noisy, drop_layer=drop_layer)
     return init_net(netE, init_type, gpu_ids)
+
+
+def define_AR(which_model_netAR, input_nc=3, init_type='kaiming', pooling='max', cnn_dim=[], cnn_pad=1, cnn_relu_slope=0.2,
+              gpu_ids=[]):
+    """reference models/networks.py:213-228: the auxiliary regressor of the continuous-label baseline"""
+    if which_model_netAR == 'alexnet':
+        base = AlexNetFeature(input_nc=input_nc, pooling='None')
+    elif which_model_netAR in ('resnet18', 'resnet34', 'resnet50'):
+        base = ResNetFeature(input_nc=input_nc, which_model=which_model_netAR)
+    elif 'resnet' in which_model_netAR:
+        raise NotImplementedError('Regressor base [%s] is outside the MI355X hot path; use alexnet, resnet18, resnet34 or resnet50'
+                                  % which_model_netAR)
+    else:
+        raise NotImplementedError('Model [%s] is not implemented.' % which_model_netAR)
+    netAR = RegressionNetwork(base, pooling=pooling, cnn_dim=cnn_dim, cnn_pad=cnn_pad, cnn_relu_slope=cnn_relu_slope)
+    return init_net(netAR, init_type, gpu_ids)
 
 
 # ------------------------------------------------------------------------- losses
@@ -570,6 +586,58 @@ class SiameseNetwork(SiameseFeature):
 
     def get_finetune_parameters(self):
         return list(self.cnn.parameters()) if self.cnn is not None else []
+
+
+class RegressionNetwork(tnn.Module):
+    """reference models/networks.py:1087-1124: SiameseFeature's trunk -> 3x3 conv head -> global pooling WITHOUT the drop layers (so
+    the head's Sequential indices, and with them the state_dict keys cnn.0 / cnn.1 / cnn.3 ..., are its own) and with a load_pretrained
+    that loads the trunk only.  state_dict keys base.*, cnn.*.  forward(x) is the fp32 (N, feature_dim, 1, 1) prediction through the
+    pooling path of the encoder; regress(x, target, delta) is the training loop's entry (regression.py:359-363): pooling, nn.MSELoss
+    and the "within delta" count as one node."""
+
+    def __init__(self, base=None, pooling='avg', cnn_dim=[], cnn_pad=1, cnn_relu_slope=0.2):
+        super().__init__()
+        self.pooling = pooling
+        self.base = base
+        if cnn_dim:
+            blk, prev = [], base.feature_dim
+            for nf in cnn_dim[:-1]:
+                blk += [hnn.Conv2d(prev, nf, kernel_size=3, stride=1, padding=cnn_pad, bias=True), hnn.BatchNorm2d(nf),
+                        tnn.LeakyReLU(cnn_relu_slope)]
+                prev = nf
+            blk += [hnn.Conv2d(prev, cnn_dim[-1], kernel_size=3, stride=1, padding=cnn_pad, bias=True)]
+            self.cnn = tnn.Sequential(*blk)
+            self.feature_dim = cnn_dim[-1]
+        else:
+            self.cnn = None
+            self.feature_dim = base.feature_dim
+
+    def _maps(self, x):
+        h = self.base.forward(x)
+        return run_sequential(self.cnn, h) if self.cnn is not None else h
+
+    def forward(self, x):
+        out = self._maps(x)
+        if self.pooling in ('avg', 'max'):
+            assert out.size(2) == out.size(3), 'global pooling expects square feature maps'
+            out = HF.global_pool(out, self.pooling == 'max')
+        return HF.cast(out, torch.float32)
+
+    def regress(self, x, target, delta):
+        """(loss, pred, hits) of one batch: nn.MSELoss()(self(x), target), the fp32 (N, feature_dim, 1, 1) prediction and the number of
+        its values within `delta` of their target (device tensors: nothing is read back).  Only `loss` carries the graph.  target: N x
+        feature_dim fp32 values on x's device."""
+        if self.pooling not in ('avg', 'max'):
+            raise NotImplementedError('pcgan_amd: RegressionNetwork.regress needs pooling avg or max, got [%s]' % self.pooling)
+        out = self._maps(x)
+        assert out.size(2) == out.size(3), 'global pooling expects square feature maps'
+        if not torch.is_grad_enabled():
+            out = out.detach()
+        return HF.pooled_mse(out, target, delta, self.pooling == 'max')
+
+    def load_pretrained(self, state_dict):
+        """only the trunk comes from the pretrained (ImageNet) file: the conv head stays as initialised (:1121-1124)"""
+        self.base.load_pretrained(state_dict)
 
 
 class BinaryNLLLoss(tnn.Module):
