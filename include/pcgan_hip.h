@@ -639,6 +639,18 @@ int pcgan_skip_join_fwd(const void* a, const void* b, void* out, int N, int Ca, 
 int pcgan_skip_join_bwd(const void* dout, const void* a, const void* b, void* da, void* db, int N, int Ca, int Cb, int HW, int act_a,
                         int act_b, int dtype, pcgan_stream_t s);
 
+/* ---- gradient fan-in (csrc/grad_fanin.hip) -----------------------------------------------------------------------------------------------
+ * y[i] = ((src[0][i] + src[1][i]) + src[2][i]) + ... : the sum autograd forms with n_src - 1 binary adds when one tensor feeds several
+ * consumers, in ONE launch.  srcs is a HOST array of n_src device pointers (1 <= n_src <= PCGAN_ADD_N_MAX; n_src == 1 is a copy); they
+ * reach the kernel inside its by-value argument, so there is no device-side pointer table and no upload.  All tensors hold n >= 1
+ * elements of `dtype` (PCGAN_F32 or PCGAN_BF16).  The sum runs strictly left to right in fp32 and there is no multiply, so fp32 tensors
+ * get the bits of the sequential fp32 sum; bf16 inputs are widened, summed in fp32 and rounded once (RNE) at the store.  y may not
+ * overlap a source (refused).  16-byte accesses with an element tail when y and every source are 16-byte aligned, element accesses
+ * otherwise; a grid-stride loop on a capped grid; no LDS, no atomics, no workspace.  Bytes moved: (n_src + 1) * n * sizeof(T).
+ * Null pointers, n_src out of range, n == 0, an unknown dtype and an aliased y are reported before any launch. */
+#define PCGAN_ADD_N_MAX 8
+int pcgan_add_n(const void* const* srcs, int n_src, void* y, size_t n, int dtype, pcgan_stream_t s);
+
 /* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),

@@ -423,6 +423,35 @@ def skip_join(a, b, act_a=ACT_NONE, act_b=ACT_NONE):
     return _SkipJoinFn.apply(a, b, act_a, act_b)
 
 
+class _FanOutFn(torch.autograd.Function):
+    """n aliases of x (no copy, no launch); the backward pass sums the gradients that arrived in ONE ops.add_n launch, in output order,
+    where autograd would chain binary adds"""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        ctx.set_materialize_grads(False)
+        return tuple(x.view_as(x) for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        live = [g for g in grads if g is not None]
+        if not live:
+            return None, None
+        if len(live) == 1:
+            return live[0], None
+        if any(g.dtype != live[0].dtype for g in live):
+            raise RuntimeError('pcgan_amd: fan_out received gradients of mixed dtypes: %s' % sorted(set(str(g.dtype) for g in live)))
+        return ops.add_n([_c(g) for g in live]), None
+
+
+def fan_out(x, n):
+    """x for n consumers: a tuple of n aliases whose gradients are summed by one kernel launch ((g0 + g1) + g2 ..., fp32, in output
+    order).  Outputs that are never used, or whose gradient is None, are skipped; a single gradient is handed on as it is."""
+    if not 1 <= n <= ops._L.ADD_N_MAX:
+        raise ValueError('pcgan_amd: fan_out serves 1 .. %d consumers, got %r' % (ops._L.ADD_N_MAX, n))
+    return _FanOutFn.apply(x, n)
+
+
 class _ChannelScaleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask_nc, scale):

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('PCGAN_LIB') or os.path.join(os.path.dirname(_HERE), '
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 PASS_FWD, PASS_BWD_DATA, PASS_BWD_WEIGHT = 0, 1, 2
 F32, BF16 = 0, 1          # storage type of activation tensors (include/pcgan_hip.h)
+ADD_N_MAX = 8             # PCGAN_ADD_N_MAX
 
 
 class ImageDesc(ctypes.Structure):
@@ -170,6 +171,7 @@ SIGNATURES = {
     'pcgan_pool_mse_fwd': (_i, [_vp] * 8 + [_sz] + [_i] * 4 + [_f, _f, _i, _vp]),
     'pcgan_skip_join_fwd': (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
     'pcgan_skip_join_bwd': (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
+    'pcgan_add_n': (_i, [ctypes.POINTER(_vp), _i, _vp, _sz, _i, _vp]),
 }
 
 _lib = None

@@ -1047,6 +1047,24 @@ def add(a, b):
     return y
 
 
+def add_n(tensors, out=None):
+    """((t0 + t1) + t2) + ... of up to lib.ADD_N_MAX equally shaped activation tensors in one launch (csrc/grad_fanin.hip): fp32 sums left
+    to right, one rounding at the store.  The result is a fresh tensor (one source: a copy) or `out`, which may not overlap a source."""
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= _L.ADD_N_MAX:
+        raise ValueError('pcgan_amd: add_n sums 1 .. %d tensors, got %d' % (_L.ADD_N_MAX, len(tensors)))
+    dt = _act(*(tensors + [out]))
+    for t in tensors[1:] + ([out] if out is not None else []):
+        if t.shape != tensors[0].shape:
+            raise RuntimeError('pcgan_amd: add_n needs equal shapes, got %s and %s' % (tuple(tensors[0].shape), tuple(t.shape)))
+    y = torch.empty_like(tensors[0]) if out is None else out
+    if y.numel() == 0:
+        return y
+    srcs = (_vp * len(tensors))(*[t.data_ptr() for t in tensors])
+    _L.check(_L.load().pcgan_add_n(srcs, len(tensors), _p(y), y.numel(), dt, _stream()), 'add_n')
+    return y
+
+
 def scale(x, scalar_dev=None, alpha=1.0):
     _chk(scalar_dev)
     dt = _act(x)
