@@ -691,8 +691,10 @@ int pcgan_timer_read(int kind, float* ms, int cap);
 /* Launch record of the implicit-GEMM family (host memory, no synchronisation): what the last forward / data-gradient call of
  * pcgan_conv2d_fwd* / pcgan_conv2d_bwd_data* that reached the implicit GEMM launched, after every clamp of a forced "hgemm_tile" /
  * "hgemm_ks".  info[0 .. n) = {sequence number (+1 per recorded launch), form (PCGAN_IGEMM_*), mode (0 forward zero padding, 1 forward
- * reflection padding, 2 data gradient, 3 data gradient gathering reflection mirrors), BM, BP (0 for the small-M kernels), K split,
- * phases}; entries past PCGAN_IGEMM_LAUNCH_INFO are 0.  The window / split / thin kernels do not record. */
+ * reflection padding, 2 data gradient, 3 data gradient gathering reflection mirrors), BM, BP, K split, phases}; entries past
+ * PCGAN_IGEMM_LAUNCH_INFO are 0.  PCGAN_IGEMM_SMALLM has no tile: there BM names the kernel (1 strip, 2 few taps, 3 generic), BP the strip
+ * kernel's instantiation as NR * 10 + MO (43, 44, 73, 74; 0 for the other two) and the K split is the strip kernel's channel split.
+ * The window / split / thin kernels do not record. */
 #define PCGAN_IGEMM_LAUNCH_INFO 7
 #define PCGAN_IGEMM_HGEMM_F16X2 1  /* hgemm_kernel, fp32 tensors as two scaled fp16 pieces */
 #define PCGAN_IGEMM_HGEMM_BF16 2   /* hgemm_kernel, bf16 tensors, one product */

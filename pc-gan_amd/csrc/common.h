@@ -69,7 +69,8 @@ __device__ __forceinline__ void report_nonfinite(unsigned* counter, bool bad) {
 int launch_weight_row_absmax(const float* w, int K, int C, int T, int by_c, float* out, hipStream_t st);
 
 // igemm_conv.hip: fold of the padded-grid gradient of a ReflectionPad2d input (also the last step of thin_conv.hip's head data gradient)
-int launch_reflect_fold(const void* padded, void* dx, int NC, int H, int W, int pad, int dtype, hipStream_t st);
+int launch_reflect_fold(const void* padded, void* dx, int NC, int H, int W, int pad, int dtype, hipStream_t st, const float* bias = nullptr,
+                        int C = 1);   // bias[plane % C] (or null) is added once, after the fold
 
 static inline int ilog2_exact(int v) {
     int l = 0;

@@ -154,15 +154,17 @@ __global__ void repack_bwd_multi_kernel(PackBwdArgs a) {
     }
 }
 
-// fold the gradient of a reflection-padded tensor back onto the unpadded tensor
+// fold the gradient of a reflection-padded tensor back onto the unpadded tensor (+ bias[plane % C], once per element: the padded
+// grid must be written WITHOUT the bias, every mirror image would carry it again)
 // grid = (row groups, planes): one thread = 4 consecutive pixels of one row, plane-local 32-bit index math
 template <typename TA>
 __global__ void reflect_fold_kernel(const TA* __restrict__ t, TA* __restrict__ dx, int NC, int H, int W,
-                                    int pad) {
+                                    int pad, const float* __restrict__ bias, int C) {
     const int Hp = H + 2 * pad, Wp = W + 2 * pad;
     const int W4 = (W + 3) >> 2;
     const TA* tp = t + (size_t)blockIdx.y * Hp * Wp;
     TA* dp = dx + (size_t)blockIdx.y * H * W;
+    const float bv = bias ? bias[blockIdx.y % C] : 0.f;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H * W4; i += gridDim.x * blockDim.x) {
         const int y = i / W4, x0 = (i - y * W4) * 4;
         int ys[3], ny = 0;
@@ -181,6 +183,10 @@ __global__ void reflect_fold_kernel(const TA* __restrict__ t, TA* __restrict__ d
                 if (x >= W - 1 - pad && x <= W - 2) v += ld1(row + pad + 2 * (W - 1) - x);
                 acc[j] += v;
             }
+        }
+        if (bias) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += bv;
         }
         if ((W & 3) == 0) {
             st4(dp + y * W + x0, make_float4(acc[0], acc[1], acc[2], acc[3]));
@@ -227,6 +233,8 @@ static int check_desc(const pcgan_conv_desc* d) {
     return 0;
 }
 
+// (tests/conv_f32_cases.py restates chunked_k, cg4_k, may_split, choose_tile, bwd_plan and the part-workspace rules in Python to pin the
+// instantiation each test case runs: a retune here must be mirrored there)
 // tile choice: the largest tile that still gives the 256 CUs >= ~1.5 workgroups each; problems with few
 // pixels but a long K loop (the encoder's 7x7 / 14x14 stages, the PatchGAN's 16x16 stage) keep the big tile
 // and are cut along K instead (split-K, partial sums reduced by splitk_reduce_kernel)
@@ -465,13 +473,13 @@ extern "C" int pcgan_conv2d_fwd_packed(const pcgan_conv_desc* d, const void* x, 
 
 namespace pcgan {
 // dx = the gradient of a reflection-padded tensor `padded` [NC][H + 2 pad][W + 2 pad] folded back onto the unpadded grid
-int launch_reflect_fold(const void* padded, void* dx, int NC, int H, int W, int pad, int dtype, hipStream_t st) {
+int launch_reflect_fold(const void* padded, void* dx, int NC, int H, int W, int pad, int dtype, hipStream_t st, const float* bias, int C) {
     PCGAN_CHECK(NC <= 65535, "conv2d_bwd_data: more than 65535 planes in the reflect fold");
     const dim3 grid((H * ((W + 3) / 4) + 255) / 256, NC);
     if (dtype == PCGAN_BF16)
-        hipLaunchKernelGGL(reflect_fold_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)padded, (bf16*)dx, NC, H, W, pad);
+        hipLaunchKernelGGL(reflect_fold_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)padded, (bf16*)dx, NC, H, W, pad, bias, C);
     else
-        hipLaunchKernelGGL(reflect_fold_kernel<float>, grid, dim3(256), 0, st, (const float*)padded, (float*)dx, NC, H, W, pad);
+        hipLaunchKernelGGL(reflect_fold_kernel<float>, grid, dim3(256), 0, st, (const float*)padded, (float*)dx, NC, H, W, pad, bias, C);
     PCGAN_LAUNCH_CHECK();
     return 0;
 }
@@ -592,7 +600,8 @@ static int conv2d_bwd_data_impl(const pcgan_conv_desc* d, const void* dy, const 
 
     IgemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.X = dy; a.Y = out; a.bias = bias; a.dtype = d->dtype;
+    a.X = dy; a.Y = out; a.dtype = d->dtype;
+    a.bias = pl.padded ? nullptr : bias;   // padded fallback: the fold adds it, once per element
     a.M = d->C; a.N = d->N; a.Cg = d->K; a.Cgp = Kgp; a.Hg = d->P; a.Wg = d->Q;
     a.Yh = H; a.Yw = W;
     a.ostep = stv; a.sl = ilog2_exact(stv); a.pad = pl.pad; a.tstep = stv;
@@ -623,7 +632,7 @@ static int conv2d_bwd_data_impl(const pcgan_conv_desc* d, const void* dy, const 
     // split-K partials live behind the A matrices (not with the padded-grid fallback or uncovered phases)
     float* part = (bwd_part_bytes(d) && !pl.padded && !pl.need_zero) ? (float*)((char*)ws + a_bytes) : nullptr;
     if (launch_igemm(pl.fused ? MODE_BWD_REFLECT : MODE_BWD, a, st, part, bwd_part_bytes(d))) return 2;
-    if (pl.padded) return pcgan::launch_reflect_fold(out, dx, d->N * d->C, d->H, d->W, d->pad, d->dtype, st);
+    if (pl.padded) return pcgan::launch_reflect_fold(out, dx, d->N * d->C, d->H, d->W, d->pad, d->dtype, st, bias, d->C);
     return 0;
 }
 

@@ -375,25 +375,26 @@ int launch_pack_strip(const float* A, float* Ws, int M, int Cg, int Cgp, int nR,
 // 3 modes x 2 storage types of: smallm_strip_kernel<MODE, NR = 4 | 7, MO = 3 | 4>, smallm_conv_fewtaps_kernel, smallm_conv_kernel
 enum { SM_STRIP, SM_FEWTAPS, SM_GENERIC };
 template <int MODE>
-static void launch_mode(int kernel, const IgemmArgs& a, dim3 grid, int maxR, hipStream_t st) {
+static void launch_mode(int kernel, const IgemmArgs& a, dim3 grid, int nr, int mo, hipStream_t st) {
     if (kernel == SM_FEWTAPS) LAUNCH_TA(a.dtype, smallm_conv_fewtaps_kernel, grid, a, MODE);
     else if (kernel == SM_GENERIC) LAUNCH_TA(a.dtype, smallm_conv_kernel, grid, a, MODE);
-    else if (maxR <= 4 && a.M <= 3) LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 4, 3);
-    else if (maxR <= 4) LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 4, 4);
-    else if (a.M <= 3) LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 7, 3);
+    else if (nr == 4 && mo == 3) LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 4, 3);
+    else if (nr == 4) LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 4, 4);
+    else if (mo == 3) LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 7, 3);
     else LAUNCH_TA(a.dtype, smallm_strip_kernel, grid, a, MODE, 7, 4);
 }
-static int launch_kernel(int mode, int kernel, const IgemmArgs& a, dim3 grid, int maxR, hipStream_t st) {
+static int launch_kernel(int mode, int kernel, const IgemmArgs& a, dim3 grid, int nr, int mo, hipStream_t st) {
     switch (mode == MODE_BWD_REFLECT ? MODE_BWD : mode) {   // no mirror-gather form here: the plain data gradient
-        case MODE_FWD_ZERO: launch_mode<MODE_FWD_ZERO>(kernel, a, grid, maxR, st); break;
-        case MODE_FWD_REFLECT: launch_mode<MODE_FWD_REFLECT>(kernel, a, grid, maxR, st); break;
-        default: launch_mode<MODE_BWD>(kernel, a, grid, maxR, st); break;
+        case MODE_FWD_ZERO: launch_mode<MODE_FWD_ZERO>(kernel, a, grid, nr, mo, st); break;
+        case MODE_FWD_REFLECT: launch_mode<MODE_FWD_REFLECT>(kernel, a, grid, nr, mo, st); break;
+        default: launch_mode<MODE_BWD>(kernel, a, grid, nr, mo, st); break;
     }
     PCGAN_LAUNCH_CHECK();
     return 0;
 }
 
 // vector-ALU path; ph[].A already holds the transposed [Kp][4] weights
+// (tests/conv_f32_cases.py restates the kernel choice and the channel split below in Python: a retune here must be mirrored there)
 int launch_smallm(int mode, IgemmArgs& a, int pmax, hipStream_t st, float* part_ws, size_t part_bytes) {
     PCGAN_CHECK(a.x_bytes < SM_INV, "small-M conv: gathered tensor must be < 1 GiB");
     for (int i = 0; i < a.nphase; ++i)
@@ -407,6 +408,7 @@ int launch_smallm(int mode, IgemmArgs& a, int pmax, hipStream_t st, float* part_
         maxstrips = ns > maxstrips ? ns : maxstrips;
         maxtaps = a.ph[i].nR * a.ph[i].nS > maxtaps ? a.ph[i].nR * a.ph[i].nS : maxtaps;
     }
+    const int nr = maxR <= 4 ? 4 : 7, mo = a.M <= 3 ? 3 : 4;   // the strip kernel's NR / MO: launched and recorded from these
     const bool unit = mode == MODE_BWD || mode == MODE_BWD_REFLECT || (a.sl == 0 && a.ostep == 1);
     if (unit && maxR >= 3 && maxR <= 7 && minH >= 8) {   // (1-2 row taps: nothing to reuse)
         // few strips but many channels (the last PatchGAN conv, 512 -> 1 on 14x14): cut the channels over blockIdx.z
@@ -421,15 +423,16 @@ int launch_smallm(int mode, IgemmArgs& a, int pmax, hipStream_t st, float* part_
         }
         a.ksplit = ks;
         a.Ypart = part_ws;
-        record_launch(PCGAN_IGEMM_SMALLM, mode, 0, 0, ks, a.nphase);
+        // small-M record: bm = kernel (1 strip | 2 few taps | 3 generic), bp = NR * 10 + MO of the strip instantiation
+        record_launch(PCGAN_IGEMM_SMALLM, mode, 1, nr * 10 + mo, ks, a.nphase);
         const dim3 gs((unsigned)((maxstrips + 63) / 64), (unsigned)a.nphase, (unsigned)ks);
-        if (int e = launch_kernel(mode, SM_STRIP, a, gs, maxR, st)) return e;
+        if (int e = launch_kernel(mode, SM_STRIP, a, gs, nr, mo, st)) return e;
         if (ks > 1 && launch_splitk_reduce(a.dtype, st, part_ws, a.Y, a.bias, ks, out_elems, a.M, a.Yh * a.Yw, a.act, a.slope)) return 2;
         return 0;
     }
-    record_launch(PCGAN_IGEMM_SMALLM, mode, 0, 0, 1, a.nphase);
-    if (maxtaps <= 9) return launch_kernel(mode, SM_FEWTAPS, a, dim3((unsigned)((pmax + 255) / 256), (unsigned)a.nphase), maxR, st);
-    return launch_kernel(mode, SM_GENERIC, a, dim3((unsigned)((pmax + 63) / 64), (unsigned)a.nphase), maxR, st);
+    record_launch(PCGAN_IGEMM_SMALLM, mode, maxtaps <= 9 ? 2 : 3, 0, 1, a.nphase);
+    if (maxtaps <= 9) return launch_kernel(mode, SM_FEWTAPS, a, dim3((unsigned)((pmax + 255) / 256), (unsigned)a.nphase), nr, mo, st);
+    return launch_kernel(mode, SM_GENERIC, a, dim3((unsigned)((pmax + 63) / 64), (unsigned)a.nphase), nr, mo, st);
 }
 
 }  // namespace pcgan

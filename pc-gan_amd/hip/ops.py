@@ -982,7 +982,8 @@ IGEMM_MODES = {0: 'fwd_zero', 1: 'fwd_reflect', 2: 'dgrad', 3: 'dgrad_reflect'}
 
 def igemm_last_launch():
     """what the last implicit-GEMM launch was (pcgan_igemm_last_launch, host memory): {'seq', 'form', 'mode', 'bm', 'bp', 'ks', 'nphase'}
-    with form / mode as names; seq grows by one per recorded launch"""
+    with form / mode as names; seq grows by one per recorded launch.  form 'smallm' has no tile: bm = 1 strip | 2 few-taps | 3 generic
+    kernel, bp = NR * 10 + MO of the strip kernel (43, 44, 73, 74; else 0), ks = the strip kernel's channel split"""
     buf = (ctypes.c_int * 7)()
     _L.check(_L.load().pcgan_igemm_last_launch(buf, 7), 'igemm_last_launch')
     seq, form, mode, bm, bp, ks, nph = list(buf)
