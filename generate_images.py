@@ -33,14 +33,17 @@ def main(argv=None):
     opt.nThreads, opt.batchSize, opt.serial_batches, opt.no_flip, opt.display_id, opt.sorted = 1, 1, True, True, -1, True
     if not opt.output_dir:
         raise ValueError('generate_images.py needs --output_dir')
-    if not hasattr(opt, 'embedding_bins') and opt.model != 'wsgan_cont':
-        raise ValueError('generate_images.py drives wsgan_emb and wsgan_cont (--model wsgan_emb / wsgan_cont)')
+    if not hasattr(opt, 'embedding_bins') and opt.model not in ('wsgan_cont', 'wsgan_disc'):
+        raise ValueError('generate_images.py drives wsgan_emb, wsgan_cont and wsgan_disc (--model wsgan_emb / wsgan_cont / wsgan_disc)')
     dataset = CreateDataLoader(opt).load_data()
     model = create_model(opt)
     model.setup(opt)
     util.mkdirs([opt.output_dir])
-    # the classes: rating bins of wsgan_emb, attribute bins (--attr_bins) of wsgan_cont
-    n_bins = len(model.embedding_bins if hasattr(model, 'embedding_bins') else model.attr_bins)
+    # the classes: rating bins of wsgan_emb, attribute bins (--attr_bins) of wsgan_cont, --num_classes of wsgan_disc
+    if opt.model == 'wsgan_disc':
+        n_bins = opt.num_classes
+    else:
+        n_bins = len(model.embedding_bins if hasattr(model, 'embedding_bins') else model.attr_bins)
     labels = None
     if opt.how_to_sample == 'label':
         if opt.sample_label_file:
@@ -60,7 +63,7 @@ def main(argv=None):
                 image = model.sample_from_label(label)
             else:
                 if not (hasattr(model, 'real_B') or hasattr(model, 'attr_B')):
-                    raise ValueError('--how_to_sample prior needs a pair dataset (--dataset_mode wsgan_emb / wsgan_cont): the rating comes from B')
+                    raise ValueError('--how_to_sample prior needs a pair dataset (--dataset_mode wsgan_emb / wsgan_cont): the rating or attribute comes from B')
                 image = model.sample_from_prior()
                 label = int(data['label'][0]) if 'label' in data else 0
             stem = os.path.splitext(ntpath.basename(model.get_image_paths()[0]))[0]

@@ -651,6 +651,26 @@ int pcgan_skip_join_bwd(const void* dout, const void* a, const void* b, void* da
 #define PCGAN_ADD_N_MAX 8
 int pcgan_add_n(const void* const* srcs, int n_src, void* y, size_t n, int dtype, pcgan_stream_t s);
 
+/* ---- history of generated images (csrc/image_pool.hip) -----------------------------------------------------------------------------------
+ * The call site it replaces is the per-image unsqueeze / clone / cat loop of the reference's ImagePool.query, util/image_pool.py:12-32.
+ * x and y hold n_img images of n elements of `dtype` (PCGAN_F32 or PCGAN_BF16), pool holds pool_size such images; all contiguous.  plan
+ * is a HOST array of n_img int32, one decision per image, carried out IN ORDER i = 0 .. n_img - 1:
+ *     plan[i] <  0           pass      y[i] = x[i]
+ *     plan[i] == 2 * s       store     pool[s] = x[i]; y[i] = x[i]
+ *     plan[i] == 2 * s + 1   exchange  y[i] = old pool[s]; pool[s] = x[i]
+ * Later images see earlier images' writes (two images may name one slot: the second receives the first).  The plan reaches the kernel
+ * inside its by-value argument, PCGAN_POOL_PLAN_MAX entries per launch; a longer batch takes consecutive launches on the same stream,
+ * ceil(n_img / PCGAN_POOL_PLAN_MAX) in all.  A thread owns one index within the image and walks the images serially, so every pool
+ * address is read and written by one thread in program order: no atomics, no LDS, no workspace.  Pure copies, bit-exact.  16-byte
+ * accesses when x, y, pool and n * sizeof(T) are multiples of 16 bytes, element accesses otherwise; a grid-stride loop on a capped grid.
+ * Null pointers, n == 0, n_img < 1, pool_size < 1, a slot outside [0, pool_size), an unknown dtype and any overlap between the byte
+ * ranges of x, y and pool are reported before any launch.  pcgan_pool_exchange_launches: kernel launches this entry has issued so far
+ * in the process (host counter). */
+#define PCGAN_POOL_PLAN_MAX 64
+int pcgan_pool_exchange(void* pool, int pool_size, const void* x, void* y, const int* plan, int n_img, size_t n, int dtype,
+                        pcgan_stream_t s);
+unsigned long long pcgan_pool_exchange_launches(void);
+
 /* ---- kernel timer (measurement only)-----------------------------------------------------------------------------------------------
  * bench.py's roofline block: HIP events on the launch stream around every launch of the three residual-block convolution kernels
  * (kind 0 forward, 1 data gradient, 2 weight gradient incl. its padded copy and reduce, 3 the weight gradient's main kernel),

@@ -133,10 +133,12 @@ class CustomDatasetDataLoader(object):
         """'<key>_raw' + '<key>_aug' -> '<key>': one image-pipeline launch per image set (A with input_nc channels, B
         with output_nc, the gray mix of the pair dataset included).  '<key>_aug' is the collated draws of decode_raw: int32
         (x0, y0, flip), or for the affine modes float64 (x0, y0, flip, m0 .. m5) -- the inverse matrix rides along"""
-        for raw_key in [k for k in batch if k.endswith('_raw')]:
+        for raw_key in [k for k in batch if isinstance(k, str) and k.endswith('_raw')]:
             key = raw_key[:-4]
-            channels = self.opt.input_nc if key.endswith('A') else self.opt.output_nc
-            batch[key] = self.gpu_transform(batch.pop(raw_key), batch.pop(key + '_aug'), out_channels=channels)
+            # an all-digit stem is a class of the class-label dataset (wsgan_disc): the finished image is filed under the int key
+            by_class = key.isdigit()
+            channels = self.opt.input_nc if by_class or key.endswith('A') else self.opt.output_nc
+            batch[int(key) if by_class else key] = self.gpu_transform(batch.pop(raw_key), batch.pop(key + '_aug'), out_channels=channels)
         return batch
 
     def load_data(self):

@@ -14,6 +14,21 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 PASS_FWD, PASS_BWD_DATA, PASS_BWD_WEIGHT = 0, 1, 2
 F32, BF16 = 0, 1          # storage type of activation tensors (include/pcgan_hip.h)
 ADD_N_MAX = 8             # PCGAN_ADD_N_MAX
+POOL_PLAN_MAX = 64        # PCGAN_POOL_PLAN_MAX: images one pcgan_pool_exchange launch serves
+POOL_PASS = -1            # plan entries of pcgan_pool_exchange: pass, store into slot s, exchange with slot s
+
+
+def pool_store(s):
+    return 2 * int(s)
+
+
+def pool_swap(s):
+    return 2 * int(s) + 1
+
+
+def pool_exchange_launches():
+    """kernel launches pcgan_pool_exchange has issued so far in this process"""
+    return int(load().pcgan_pool_exchange_launches())
 
 
 class ImageDesc(ctypes.Structure):
@@ -172,6 +187,8 @@ SIGNATURES = {
     'pcgan_skip_join_fwd': (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
     'pcgan_skip_join_bwd': (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     'pcgan_add_n': (_i, [ctypes.POINTER(_vp), _i, _vp, _sz, _i, _vp]),
+    'pcgan_pool_exchange': (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(_i), _i, _sz, _i, _vp]),
+    'pcgan_pool_exchange_launches': (ctypes.c_ulonglong, []),
 }
 
 _lib = None

@@ -1066,6 +1066,26 @@ def add_n(tensors, out=None):
     return y
 
 
+def pool_exchange(pool, x, plan):
+    """The reference's ImagePool.query loop (util/image_pool.py:12-32) on the device, one launch per lib.POOL_PLAN_MAX images
+    (csrc/image_pool.hip): pool (S, ...) and x (B, ...) hold images of one shape and storage type, plan holds B entries carried out in
+    order -- lib.POOL_PASS, lib.pool_store(s) or lib.pool_swap(s).  Returns the batch the caller receives, a fresh tensor; pool is
+    updated in place."""
+    dt = _act(pool, x)
+    if pool.dim() < 2 or x.dim() != pool.dim() or x.shape[1:] != pool.shape[1:]:
+        raise RuntimeError('pcgan_amd: pool_exchange needs a pool (S, ...) and a batch (B, ...) of one image shape, got %s and %s'
+                           % (tuple(pool.shape), tuple(x.shape)))
+    plan = [int(v) for v in plan]
+    if len(plan) != x.shape[0]:
+        raise RuntimeError('pcgan_amd: pool_exchange got a plan of %d entries for %d images' % (len(plan), x.shape[0]))
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    _L.check(_L.load().pcgan_pool_exchange(_p(pool), pool.shape[0], _p(x), _p(y), (ctypes.c_int * len(plan))(*plan), len(plan),
+                                           x[0].numel(), dt, _stream()), 'pool_exchange')
+    return y
+
+
 def scale(x, scalar_dev=None, alpha=1.0):
     _chk(scalar_dev)
     dt = _act(x)

@@ -184,6 +184,19 @@ def define_E(which_model_netE, input_nc=3, init_type='kaiming', pooling='max', c
     return init_net(netE, init_type, gpu_ids)
 
 
+def define_AC(which_model_netAC, input_nc=3, init_type='normal', num_classes=0, pooling='avg', dropout=0.5, gpu_ids=[]):
+    """reference models/networks.py:197-209: the auxiliary classifier of the class-label baseline.  `pooling` and `dropout` reach only
+    the reference's AlexNetLite; its ResNet ignores them, and so does this one."""
+    if which_model_netAC in ('resnet18', 'resnet34', 'resnet50'):
+        netAC = ResNet(input_nc=input_nc, num_classes=num_classes, which_model=which_model_netAC)
+    elif which_model_netAC in ('alexnet', 'alexnet_lite') or 'resnet' in which_model_netAC:
+        raise NotImplementedError('Auxiliary classifier [%s] is outside the MI355X hot path; use resnet18, resnet34 or resnet50'
+                                  % which_model_netAC)
+    else:
+        raise NotImplementedError('Auxiliary classifier name [%s] is not recognized' % which_model_netAC)
+    return init_net(netAC, init_type, gpu_ids)
+
+
 def define_AR(which_model_netAR, input_nc=3, init_type='kaiming', pooling='max', cnn_dim=[], cnn_pad=1, cnn_relu_slope=0.2,
               gpu_ids=[]):
     """reference models/networks.py:213-228: the auxiliary regressor of the continuous-label baseline"""
