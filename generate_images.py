@@ -11,6 +11,7 @@ test options (options/test_options.py:20-22: --how_to_sample, --sample_label_fil
                           normalised bin centre embedding_bins[l]) (reference models/wsgan_emb_model.py:294-298).  The class of
                           image i is line i of --sample_label_file (cycled) or, without a file, uniform over the bins under --seed.
   --how_to_sample prior   needs a pair dataset (--dataset_mode wsgan_emb): `model.sample_from_prior()` = G(A, E(B)) (:279-292).
+                          Refused for --model wsgan_bigan, which is sampled by class only (its classes are --attr_bins).
 
 Files: <output_dir>/<label>_<index>_<stem>.png -- the class first, so that the attribute parsers of the evaluation scripts
 (`float(name.split('_')[0])`, siamese.py:299-303) read it back.  compute_fid_score.py then takes <output_dir> as its first path."""
@@ -33,13 +34,17 @@ def main(argv=None):
     opt.nThreads, opt.batchSize, opt.serial_batches, opt.no_flip, opt.display_id, opt.sorted = 1, 1, True, True, -1, True
     if not opt.output_dir:
         raise ValueError('generate_images.py needs --output_dir')
-    if not hasattr(opt, 'embedding_bins') and opt.model not in ('wsgan_cont', 'wsgan_disc'):
-        raise ValueError('generate_images.py drives wsgan_emb, wsgan_cont and wsgan_disc (--model wsgan_emb / wsgan_cont / wsgan_disc)')
+    if not hasattr(opt, 'embedding_bins') and opt.model not in ('wsgan_cont', 'wsgan_disc', 'wsgan_bigan'):
+        raise ValueError('generate_images.py drives wsgan_emb, wsgan_cont and wsgan_disc, and wsgan_bigan by class '
+                         '(--model wsgan_emb / wsgan_cont / wsgan_disc / wsgan_bigan)')
+    if opt.model == 'wsgan_bigan' and opt.how_to_sample != 'label':
+        raise ValueError('generate_images.py samples --model wsgan_bigan by class only (--how_to_sample label); '
+                         '--how_to_sample prior is not supported for it')
     dataset = CreateDataLoader(opt).load_data()
     model = create_model(opt)
     model.setup(opt)
     util.mkdirs([opt.output_dir])
-    # the classes: rating bins of wsgan_emb, attribute bins (--attr_bins) of wsgan_cont, --num_classes of wsgan_disc
+    # the classes: rating bins of wsgan_emb, attribute bins (--attr_bins) of wsgan_cont and wsgan_bigan, --num_classes of wsgan_disc
     if opt.model == 'wsgan_disc':
         n_bins = opt.num_classes
     else:

@@ -651,6 +651,21 @@ int pcgan_skip_join_bwd(const void* dout, const void* a, const void* b, void* da
 #define PCGAN_ADD_N_MAX 8
 int pcgan_add_n(const void* const* srcs, int n_src, void* y, size_t n, int dtype, pcgan_stream_t s);
 
+/* ---- backward pass of pcgan_concat_z (csrc/concat_bwd.hip) ---------------------------------------------------------------------------------
+ * dy[N][C + nz][HW] is an activation tensor of `dtype` (PCGAN_F32 or PCGAN_BF16), contiguous.  In ONE launch:
+ *     dimg[N][C][HW]    (dtype)  a bit-exact copy of dy[:, :C]
+ *     dz[z_batch][nz]   (fp32)   dz[n][j] = the sum over the plane dy[n][C + j][:], accumulated in fp32 (ratings stay fp32, as in the
+ *                                forward kernel); with z_batch == 1 (one rating for the batch) dz[0][j] = ((s_0 + s_1) + ...) + s_{N-1},
+ *                                s_n the plane sums in ascending n.
+ * dimg or dz may be NULL (not wanted), not both; a NULL output is not computed and its planes of dy are not read, so a dz-only call
+ * touches N * nz planes.  The workgroups of the one grid are split between the two jobs; a plane is summed by one 256-lane workgroup
+ * (per-lane fp32 partial sums in index order, a wave64 butterfly, the four wave results in wave order through LDS).  No atomics, no
+ * workspace, no second launch: the order of the additions is fixed by the launch geometry, two calls give the same bits.  16-byte
+ * accesses when HW * sizeof(T) and every pointer handed in are multiples of 16, element accesses otherwise.  dy null, both outputs
+ * null, N, C, HW or nz <= 0, z_batch outside {1, N}, an unknown dtype and sizes whose products overflow int are reported before any
+ * launch. */
+int pcgan_concat_z_bwd(const void* dy, void* dimg, float* dz, int N, int C, int nz, int HW, int z_batch, int dtype, pcgan_stream_t s);
+
 /* ---- history of generated images (csrc/image_pool.hip) -----------------------------------------------------------------------------------
  * The call site it replaces is the per-image unsqueeze / clone / cat loop of the reference's ImagePool.query, util/image_pool.py:12-32.
  * x and y hold n_img images of n elements of `dtype` (PCGAN_F32 or PCGAN_BF16), pool holds pool_size such images; all contiguous.  plan

@@ -5,6 +5,9 @@ applied twice per step with the first output feeding the second pass; the discri
 sees the same fake image in two different graphs).  Autograd bookkeeping is the only
 thing torch does here -- every forward/backward computation is a libpcgan_hip.so kernel.
 """
+import contextlib
+import os
+
 import torch
 
 from . import ops
@@ -394,8 +397,68 @@ class _ConcatZFn(torch.autograd.Function):
         return dimg, dz
 
 
+class _ConcatZFusedFn(torch.autograd.Function):
+    """_ConcatZFn with the backward pass as ONE launch (ops.concat_z_bwd) that computes only what is asked for: with a rating that needs a
+    gradient beside an image that needs none, the image planes of dy are neither copied nor read.  dimg has the bits of _ConcatZFn's; dz is
+    the same fp32 sum in another (fixed) order."""
+
+    @staticmethod
+    def forward(ctx, img, z):
+        img = _c(img)
+        z2 = _c(z.reshape(z.size(0), z.size(1)))
+        ctx.shapes = (img.shape, z.shape)
+        return ops.concat_z(img, z2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ishape, zshape = ctx.shapes
+        want_img, want_z = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_img or want_z):
+            return None, None
+        dimg, dz = ops.concat_z_bwd(_c(dy), ishape[1], zshape[0], want_img, want_z)
+        return dimg, (dz.reshape(zshape) if want_z else None)
+
+
+# PCGAN_CONCATZ_FUSED=0 (read once, when this module is imported) keeps _ConcatZFn even inside fused_concat_bwd() -- the A/B switch of
+# scripts/bench_bigan.py, as PCGAN_FANOUT is for fan_out
+_CONCATZ_FUSED_ENV = os.environ.get('PCGAN_CONCATZ_FUSED', '1') != '0'
+_concatz_fused = False
+
+
+@contextlib.contextmanager
+def fused_concat_bwd(enabled=True):
+    """concat_z calls made inside take the one-launch backward pass (_ConcatZFusedFn) where it has been measured to pay (fused_serves: a
+    rating that needs a gradient; a shared one only over few, small planes).  Read when concat_z runs, i.e. at forward time: the backward
+    pass of a graph built inside may run anywhere."""
+    global _concatz_fused
+    old, _concatz_fused = _concatz_fused, bool(enabled)
+    try:
+        yield
+    finally:
+        _concatz_fused = old
+
+
+# Where the one-launch backward pass is taken (measured: scripts/bench_bigan.py, profiles/bigan_step.json, DESIGN.md section 9).
+#   * The rating needs no gradient: the chain is then ONE strided copy, there is nothing to fuse, and the two are level to within the
+#     spread between runs -- the default function stays.
+#   * One rating shared by the batch (z_batch == 1 < N): ONE workgroup of the fused kernel walks all N planes of a rating channel, at
+#     1.1 us (32 KiB plane) to 6.4 us (256 KiB) per plane, where the chain's plane sums use N workgroups and the whole chain takes
+#     35 us.  Measured at 128 x 128: the fused call wins at N = 10 (fp32, 640 KiB of planes) and N = 16 (bf16, 512 KiB), loses at
+#     N = 16 (fp32, 1 MiB) and N = 24 (bf16, 768 KiB) and everywhere above.  It is taken inside the measured winning region only.
+FUSED_SHARED_MAX_PLANES = 16
+FUSED_SHARED_MAX_BYTES = 640 << 10
+
+
+def fused_serves(N, plane_bytes, z_batch):
+    """whether the one-launch backward pass is taken for the gradient of a rating of batch `z_batch` joined to N planes of plane_bytes"""
+    return z_batch == N or (N <= FUSED_SHARED_MAX_PLANES and N * plane_bytes <= FUSED_SHARED_MAX_BYTES)
+
+
 def concat_z(img, z):
     """torch.cat((img, z broadcast over H,W), 1); z is (B or 1, nz, 1, 1)."""
+    if _concatz_fused and _CONCATZ_FUSED_ENV and z.requires_grad:
+        if fused_serves(img.size(0), img.size(2) * img.size(3) * img.element_size(), z.size(0)):
+            return _ConcatZFusedFn.apply(img, z)
     return _ConcatZFn.apply(img, z)
 
 

@@ -187,6 +187,7 @@ SIGNATURES = {
     'pcgan_skip_join_fwd': (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
     'pcgan_skip_join_bwd': (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     'pcgan_add_n': (_i, [ctypes.POINTER(_vp), _i, _vp, _sz, _i, _vp]),
+    'pcgan_concat_z_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'pcgan_pool_exchange': (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(_i), _i, _sz, _i, _vp]),
     'pcgan_pool_exchange_launches': (ctypes.c_ulonglong, []),
 }

@@ -1104,6 +1104,23 @@ def concat_z(img, z):
     return out
 
 
+def concat_z_bwd(dy, C, z_batch, want_img=True, want_z=True):
+    """The backward pass of concat_z in one launch (csrc/concat_bwd.hip): dy is (N, C + nz, H, W); returns (dimg, dz) with dimg =
+    dy[:, :C] as a fresh contiguous tensor and dz the fp32 (z_batch, nz) plane sums of dy[:, C:], summed over the batch in ascending n when
+    z_batch == 1.  An output that is not wanted is None and its part of dy is not read."""
+    dt = _act(dy)
+    if dy.dim() != 4 or not 0 < C < dy.shape[1]:
+        raise RuntimeError('pcgan_amd: concat_z_bwd takes dy (N, C + nz, H, W) with nz >= 1, got %s and C = %r' % (tuple(dy.shape), C))
+    if not (want_img or want_z):
+        raise RuntimeError('pcgan_amd: concat_z_bwd needs at least one output')
+    N, Ct, H, W = dy.shape
+    nz = Ct - C
+    dimg = torch.empty((N, C, H, W), dtype=dy.dtype, device=dy.device) if want_img else None
+    dz = torch.empty((z_batch, nz), dtype=torch.float32, device=dy.device) if want_z else None
+    _L.check(_L.load().pcgan_concat_z_bwd(_p(dy), _p(dimg), _p(dz), N, C, nz, H * W, z_batch, dt, _stream()), 'concat_z_bwd')
+    return dimg, dz
+
+
 def _join_acts(what, act_a, act_b):
     for act in (act_a, act_b):
         if act not in (ACT_NONE, _L.ACT_RELU):
