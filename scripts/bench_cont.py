@@ -105,7 +105,7 @@ def _build(tmp):
 
 def bench_step(res, steps):
     import torch
-    from pcgan_amd.models import wsgan_cont_model as M
+    from pcgan_amd.models import wsgan_shared as M
     model = _build(tempfile.mkdtemp(prefix='pcgan_cont_bench_'))
     g = torch.Generator().manual_seed(1234)
     batch = {'A': torch.rand(32, 3, 128, 128, generator=g) * 2 - 1, 'B': torch.rand(32, 3, 128, 128, generator=g) * 2 - 1,

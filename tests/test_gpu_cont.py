@@ -190,7 +190,7 @@ def _one_step(tmp_path, sub, name='aux_on_fake_L1'):
 
 def test_fan_out_switch_and_determinism(tmp_path, dev, monkeypatch):
     from pcgan_amd.hip import ops
-    from pcgan_amd.models import wsgan_cont_model as M
+    from pcgan_amd.models import wsgan_shared as M
     assert M._FANOUT is (os.environ.get('PCGAN_FANOUT', '1') != '0')
     calls = []
     orig = ops.add_n
