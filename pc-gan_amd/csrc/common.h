@@ -226,7 +226,8 @@ __device__ __forceinline__ void split2h(float x, _Float16& h, _Float16& l) {
     l = (_Float16)(x - (float)h);
 }
 
-// largest v over the workgroup, thread 0 gets it (others: a partial value)
+// largest v over the workgroup (blockDim.x <= 1024, a multiple of 64); scratch: one float of LDS per wave.  Result valid in ALL threads: every
+// thread reads all the wave maxima back (the thin kernel derives each thread's sx from it)
 __device__ __forceinline__ float block_max(float v, float* scratch) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll

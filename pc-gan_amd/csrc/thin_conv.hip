@@ -100,7 +100,10 @@ __global__ void __launch_bounds__(256) thin_conv_kernel(ThinArgs a) {
     }
 
     const float sx = pow2_scale(block_max(thread_max_of_partials(a.x_amax, a.x_namax, tid, 256), red));
-    if (tid < 64) isw[tid] = 1.f / (pow2_scale(a.rowmax[mt * 64 + tid]) * sx);
+    // the two reciprocals are applied one after the other (both exact powers of two): their product leaves fp32's range when x sits at
+    // the 2^100 clamp and a filter row needs 2^28 or more (x near 1e-30, w near 1e-5: 1 / inf = 0 wrote exact zeros for results near 1e-34)
+    const float isx = 1.f / sx;
+    if (tid < 64) isw[tid] = 1.f / pow2_scale(a.rowmax[mt * 64 + tid]);
 
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
@@ -161,7 +164,7 @@ __global__ void __launch_bounds__(256) thin_conv_kernel(ThinArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int ml = wm * 32 + (r >> 2) * 8 + hi * 4 + (r & 3), m = mt * 64 + ml;
-            const float av = acc[j][r] * isw[ml];
+            const float av = acc[j][r] * isw[ml] * isx;
             bad |= is_nonfinite(av);
             a.Y[((size_t)n * a.M + m) * PQ + (size_t)oy * a.Q + ox] = act_apply(av + (a.bias ? a.bias[m] : 0.f), a.act, a.slope);
         }
