@@ -158,16 +158,21 @@ __global__ void __launch_bounds__(512) bsplit_halo_kernel(HaloArgs a) {
         sx = pow2_scale(block_max(m, red_scratch));
         __syncthreads();
     }
-    auto put_split = [&](unsigned lds, int buf, const float (&v)[4]) {
+    // sum = a sum entry of the data gradient: up to FOUR dy elements added before the split.  Four sources at the top of [2^13, 2^14)
+    // scale to as much as 4 (2^14 - 1) < 2^16, past fp16's 65504 (dy = 1 - 2^-13 everywhere: 65528, the cast gave inf and the four
+    // corner pixels of every plane NaN).  Below 2^16 the high piece saturates at 65504 and the low piece takes the rest (< 32, to
+    // 2^-7: the split keeps its 2^-22); every value the cast already kept finite splits as before, bit for bit.  From 2^16 on the
+    // maximum the scale came from was not one: that still overflows and the sentinel counts it
+    auto put_split = [&](unsigned lds, int buf, const float (&v)[4], const bool sum = false) {
         char* dst = xs_bytes + (unsigned)buf * XBUF + lds;
         if constexpr (PK == PK_F16X2) {
             hf4 h, l;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                _Float16 x, y;
-                split2h(v[j] * sx, x, y);
+                const float s = v[j] * sx;
+                _Float16 x = (_Float16)((sum && fabsf(s) < 65536.f) ? __builtin_amdgcn_fmed3f(s, -65504.f, 65504.f) : s);
                 h[j] = x;
-                l[j] = y;
+                l[j] = (_Float16)(s - (float)x);
             }
             *reinterpret_cast<hf4*>(dst) = h;
             *reinterpret_cast<hf4*>(dst + XPIECE) = l;
@@ -241,7 +246,7 @@ __global__ void __launch_bounds__(512) bsplit_halo_kernel(HaloArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     v[j] = (tofloat(tp[i][0][j]) + tofloat(tp[i][1][j])) + (tofloat(tp[i][2][j]) + tofloat(tp[i][3][j]));
-                put_split(plds[i], buf, v);
+                put_split(plds[i], buf, v, true);
             }
         }
     };
