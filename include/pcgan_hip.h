@@ -666,6 +666,37 @@ int pcgan_add_n(const void* const* srcs, int n_src, void* y, size_t n, int dtype
  * launch. */
 int pcgan_concat_z_bwd(const void* dy, void* dimg, float* dz, int N, int C, int nz, int HW, int z_batch, int dtype, pcgan_stream_t s);
 
+/* ---- Grad-CAM map and heat-map overlay of `siamese.py --mode attention` (csrc/gradcam.hip) ---------------------------------------------------
+ * pcgan_gradcam_map replaces GradCAM2.generate of the reference (util/gradcam.py:214-252, called at siamese.py:958): act and grad are
+ * [N][C][H][W] activation tensors of `dtype` (PCGAN_F32 or PCGAN_BF16, both the same), map is [N][1][H][W] fp32:
+ *     PCGAN_GCAM_RAW      abs(sum_c A)                  grad may be NULL and is neither read nor required
+ *     PCGAN_GCAM_PW       relu(sum_c g * A)
+ *     PCGAN_GCAM_CW_POS   relu(sum_c w[n][c] * A)       w[n][c] = the mean over the plane of relu(g[n][c][:][:])
+ *     PCGAN_GCAM_PW_CW    relu(sum_c (w[n][c] * g) * A)
+ * (the reference's grouped conv3d with groups = N is this per-image channel sum; every type returns [N][1][H][W] here).  bf16 is widened
+ * exactly, all arithmetic is fp32, one rounding per operation.  ONE launch, no workspace, no atomics, a summation order fixed by the
+ * launch geometry: two calls give the same bits.  The weighted types recompute the plane means in every workgroup of an image (LDS holds
+ * them: C <= 4096 there).  16-byte accesses when H * W * sizeof(T) and every pointer handed in are multiples of 16, element accesses
+ * otherwise.  An unknown type or dtype, N, C, H or W <= 0, a null act or map, a null grad with a type other than raw, more than 4096
+ * channels with a weighted type and sizes whose products overflow int are reported before any launch. */
+#define PCGAN_GCAM_RAW 0
+#define PCGAN_GCAM_PW 1
+#define PCGAN_GCAM_CW_POS 2
+#define PCGAN_GCAM_PW_CW 3
+int pcgan_gradcam_map(const void* act, const void* grad, float* map, int N, int C, int H, int W, int type, int dtype, pcgan_stream_t s);
+
+/* pcgan_heatmap_overlay replaces feature2image, tensor2image and the blend of attention_gradcam (siamese.py:401-410, 965-978), per image n
+ * of the batch (the reference takes image_tensor[0]): map is [N][Cm][H][W] fp32 with Cm = 1 (broadcast over the three channels, the
+ * reference's expand(1, 3, 224, 224)) or 3, already at image size; img is [N][3][H][W] of `dtype`, the normalised network input; mean and
+ * std are HOST arrays of 3 floats.  With lo / hi the smallest / largest of the Cm * H * W map values of image n,
+ *     out[n][c][p] = (((map - lo) / (hi - lo)) * 255) * (1 - alpha) + (((img * std[c] + mean[c]) * 255) * alpha)      (fp32, [N][3][H][W])
+ *     lohi[n] = {lo, hi}
+ * one rounding per operation (the unit is built with -ffp-contract=off).  Where hi == lo the reference divides by zero; here the heat
+ * term is 0.  One 1024-lane workgroup per image reduces and then writes, in one launch; no workspace, no atomics.  N, H or W <= 0, Cm
+ * outside {1, 3}, a null pointer, an unknown dtype and N * 3 * H * W overflowing int are reported before any launch. */
+int pcgan_heatmap_overlay(const float* map, const void* img, const float* mean, const float* std, float alpha, float* out, float* lohi,
+                          int N, int Cm, int H, int W, int dtype, pcgan_stream_t s);
+
 /* ---- history of generated images (csrc/image_pool.hip) -----------------------------------------------------------------------------------
  * The call site it replaces is the per-image unsqueeze / clone / cat loop of the reference's ImagePool.query, util/image_pool.py:12-32.
  * x and y hold n_img images of n elements of `dtype` (PCGAN_F32 or PCGAN_BF16), pool holds pool_size such images; all contiguous.  plan

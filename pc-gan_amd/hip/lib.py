@@ -15,6 +15,7 @@ PASS_FWD, PASS_BWD_DATA, PASS_BWD_WEIGHT = 0, 1, 2
 F32, BF16 = 0, 1          # storage type of activation tensors (include/pcgan_hip.h)
 ADD_N_MAX = 8             # PCGAN_ADD_N_MAX
 POOL_PLAN_MAX = 64        # PCGAN_POOL_PLAN_MAX: images one pcgan_pool_exchange launch serves
+GCAM_TYPES = {'raw': 0, 'pw': 1, 'cw_pos': 2, 'pw_cw': 3}      # PCGAN_GCAM_*: the map types of pcgan_gradcam_map
 POOL_PASS = -1            # plan entries of pcgan_pool_exchange: pass, store into slot s, exchange with slot s
 
 
@@ -190,6 +191,8 @@ SIGNATURES = {
     'pcgan_concat_z_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'pcgan_pool_exchange': (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(_i), _i, _sz, _i, _vp]),
     'pcgan_pool_exchange_launches': (ctypes.c_ulonglong, []),
+    'pcgan_gradcam_map': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'pcgan_heatmap_overlay': (_i, [_vp, _vp, ctypes.POINTER(_f), ctypes.POINTER(_f), _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -1121,6 +1121,49 @@ def concat_z_bwd(dy, C, z_batch, want_img=True, want_z=True):
     return dimg, dz
 
 
+def gradcam_map(act, grad, kind='raw'):
+    """The Grad-CAM map of a captured activation in one launch (csrc/gradcam.hip; reference util/gradcam.py: generate): act and grad are
+    (N, C, H, W) of one storage type, the result is (N, 1, H, W) fp32 -- `raw` abs(sum_c A) (grad may be None), `pw` relu(sum_c g * A),
+    `cw_pos` relu(sum_c w * A) and `pw_cw` relu(sum_c w * g * A) with w[n, c] the plane mean of relu(g[n, c])."""
+    code = _L.GCAM_TYPES.get(kind)
+    if code is None:
+        raise RuntimeError('pcgan_amd: gradcam_map type %r (one of %s)' % (kind, ' | '.join(sorted(_L.GCAM_TYPES))))
+    if kind == 'raw':
+        grad = None
+    elif grad is None:
+        raise RuntimeError('pcgan_amd: gradcam_map type %r needs the gradient' % kind)
+    dt = _act(act, grad)
+    if act.dim() != 4 or (grad is not None and grad.shape != act.shape):
+        raise RuntimeError('pcgan_amd: gradcam_map takes act and grad of one shape (N, C, H, W), got %s and %s'
+                           % (tuple(act.shape), None if grad is None else tuple(grad.shape)))
+    N, C, H, W = act.shape
+    out = torch.empty((N, 1, H, W), dtype=torch.float32, device=act.device)
+    _L.check(_L.load().pcgan_gradcam_map(_p(act), _p(grad), _p(out), N, C, H, W, code, dt, _stream()), 'gradcam_map')
+    return out
+
+
+def heatmap_overlay(hmap, img, mean, std, alpha):
+    """The heat-map overlay of `siamese.py --mode attention` in one launch (csrc/gradcam.hip; reference siamese.py:401-410, 965-978): hmap
+    (N, 1 or 3, H, W) fp32 at image size, img (N, 3, H, W) the normalised network input; returns (out, lohi) with
+    out = ((hmap - lo) / (hi - lo) * 255) * (1 - alpha) + ((img * std + mean) * 255) * alpha in fp32 and lohi (N, 2) the per-image
+    minimum and maximum of hmap.  Where hi == lo (the reference divides by zero) the heat term is 0."""
+    _chk(hmap)
+    dt = _act(img)
+    if hmap.dim() != 4 or img.dim() != 4 or img.shape[1] != 3 or hmap.shape[1] not in (1, 3) or \
+            (hmap.shape[0],) + tuple(hmap.shape[2:]) != (img.shape[0],) + tuple(img.shape[2:]):
+        raise RuntimeError('pcgan_amd: heatmap_overlay takes a map (N, 1 | 3, H, W) and an image (N, 3, H, W), got %s and %s'
+                           % (tuple(hmap.shape), tuple(img.shape)))
+    if len(mean) != 3 or len(std) != 3:
+        raise RuntimeError('pcgan_amd: heatmap_overlay takes three means and three standard deviations')
+    N, Cm, H, W = hmap.shape
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=img.device)
+    lohi = torch.empty((N, 2), dtype=torch.float32, device=img.device)
+    f3 = ctypes.c_float * 3
+    _L.check(_L.load().pcgan_heatmap_overlay(_p(hmap), _p(img), f3(*mean), f3(*std), float(alpha), _p(out), _p(lohi), N, Cm, H, W, dt,
+                                             _stream()), 'heatmap_overlay')
+    return out, lohi
+
+
 def _join_acts(what, act_a, act_b):
     for act in (act_a, act_b):
         if act not in (ACT_NONE, _L.ACT_RELU):

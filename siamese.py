@@ -15,7 +15,11 @@ augmentation is every `--transforms` mode of the loader, the reference's `resize
 (bit-exact; workers only decode and draw); `--dataroot synthetic` trains on seeded synthetic pairs whose label is decided
 by a hidden per-image score, so the loss must fall.
 
+`--mode attention` shows what a trained encoder rates: a Grad-CAM map of `--gcam_layer` (or the input gradient) per image, blended over
+the image by two HIP kernels (csrc/gradcam.hip); see attention().
+
     python siamese.py --dataroot synthetic --name elo --batch_size 32 --num_epochs 2 --pretrained_model_path ''
+    python siamese.py --mode attention --dataroot synthetic --name elo --max_dataset_size 4 --gcam_type cw_pos --gcam_save
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 siamese.py ...        # one process per GPU, RCCL
 """
 import argparse
@@ -87,6 +91,12 @@ def build_parser():
     add('--lb_or_mc', type=str, default='lb', choices=['lb', 'mc'])
     add('--seed', type=int, default=0)
     add('--max_dataset_size', type=int, default=1 << 30)
+    add('--gcam_layer', type=str, default='base.model.layer1.0.conv1', help='(--mode attention) named_modules() name of the captured layer')
+    add('--gcam_save', action='store_true', help='(--mode attention) write iter%%d_{A,B}_{x,a}.png under --gcam_dir')
+    add('--gcam_type', type=str, default='raw', choices=['raw', 'pw', 'pw_cw', 'cw_pos', 'input'],
+        help='(pcgan_amd) map type of util/gradcam.py: generate (the reference hard-codes raw), or `input`: d rating / d image')
+    add('--gcam_alpha', type=float, default=0.01, help='(pcgan_amd) weight of the image in the overlay (the reference constant)')
+    add('--gcam_dir', type=str, default='results_attn', help='(pcgan_amd) where --gcam_save writes')
     return ap
 
 
@@ -469,6 +479,62 @@ def test(opt):
     return acc
 
 
+GCAM_MEAN, GCAM_STD = (0.4914, 0.4822, 0.4465), (0.2023, 0.1994, 0.2010)      # tensor2image of the reference (siamese.py:401-404)
+
+
+def image_uint8(v):
+    """(3, H, W) fp32 in [0, 255] -> (H, W, 3) uint8: np.clip(np.rint(v), 0, 255), on the host"""
+    return np.clip(np.rint(v.detach().cpu().numpy()), 0, 255).astype(np.uint8).transpose(1, 2, 0)
+
+
+def attention(opt):
+    """`--mode attention` (reference siamese.py:944-985 with util/gradcam.py): which regions of an image drive its rating.  For every pair
+    of --datafile (batch size 1, unshuffled) and each of its two images: the map of --gcam_layer (util/gradcam.py: one pass, the captured
+    activation, the gradient of the image's own rating, ops.gradcam_map) -> upsample2d to --fineSize (bilinear, align_corners=True) ->
+    ops.heatmap_overlay with the constants of tensor2image and --gcam_alpha.  `--gcam_type input` takes d rating / d image (the
+    reference's get_attention) as a three-channel map instead.  Returns [(map_A, map_B, lohi_A, lohi_B)] per pair, on the host.
+
+    The reference's path does not run (GradCAM2.forward unpacks five outputs of a net that returns three or four; it needs visdom, cv2
+    and scipy.misc.imsave, and calls .cuda() unconditionally); what it evidently means is built, with these differences:
+      * the net is the trained SiameseNetwork (build_net with the checkpoint, as --mode test), one `forward_once` per image;
+      * each image's map uses the gradient of its own rating, the reference keeps the last hook of feature1 - feature2 (util/gradcam.py);
+      * both images are overlaid (the reference computes the map once and shows image B only), image_tensor[0] being each image;
+      * where the map is constant (hi == lo) the reference divides by zero, here the heat term is 0;
+      * PNGs are written with Pillow from np.clip(np.rint(v), 0, 255) of the kernel's fp32 output; scipy.misc.imsave rescaled every array
+        by its own range a second time, so its files were stretched to 0 .. 255 whatever the overlay held;
+      * no visdom window, no time.sleep(1), no debugging prints; the guided-ReLU variant (update_relus) is out of scope."""
+    from pcgan_amd.hip import functional as HF, ops
+    from pcgan_amd.util.gradcam import GradCAM
+    device = _device(opt)
+    opt.continue_train = True                  # build_net then loads <which_epoch>_net.pth
+    net = build_net(opt, device)
+    data = PairDataset(opt, opt.dataroot, opt.datafile)
+    tf = gpu_pipeline(opt, data, device)
+    loader = make_loader(opt, data, tf, shuffle=False, batch_size=1)
+    gcam = GradCAM(net, opt.gcam_layer)
+    if opt.gcam_save:
+        from PIL import Image
+        os.makedirs(opt.gcam_dir, exist_ok=True)
+    results = []
+    for i, batch in enumerate(loader):
+        img0, img1, _ = pair_batch(batch, tf, device)
+        maps, ranges = [], []
+        for tag, img in (('A', img0), ('B', img1)):
+            img = img.contiguous()
+            m = gcam.input_gradient(img) if opt.gcam_type == 'input' else gcam.map(img, opt.gcam_type)
+            up = HF.upsample2d(HF.cast(m, torch.float32), opt.fineSize).contiguous()
+            over, lohi = ops.heatmap_overlay(up, img, GCAM_MEAN, GCAM_STD, opt.gcam_alpha)
+            if opt.gcam_save:
+                plain, _ = ops.heatmap_overlay(up, img, GCAM_MEAN, GCAM_STD, 1.0)      # alpha = 1: the de-normalised image alone
+                Image.fromarray(image_uint8(plain[0])).save(os.path.join(opt.gcam_dir, 'iter%d_%s_x.png' % (i, tag)))
+                Image.fromarray(image_uint8(over[0])).save(os.path.join(opt.gcam_dir, 'iter%d_%s_a.png' % (i, tag)))
+            maps.append(m.detach().cpu())
+            ranges.append(lohi.cpu())
+        results.append((maps[0], maps[1], ranges[0], ranges[1]))
+        print('--> iter#%d' % i)
+    return results
+
+
 if __name__ == '__main__':
     options = build_parser().parse_args()
     if options.mode == 'train':
@@ -477,6 +543,8 @@ if __name__ == '__main__':
         embedding(options)
     elif options.mode == 'test':
         test(options)
+    elif options.mode == 'attention':
+        attention(options)
     else:
-        raise NotImplementedError('pcgan_amd: siamese.py --mode %s is outside the MI355X hot path (train | embedding | test; the '
-                                  'optimize / attention modes need visdom / Grad-CAM tooling)' % options.mode)
+        raise NotImplementedError('pcgan_amd: siamese.py --mode %s is outside the MI355X hot path (train | embedding | test | '
+                                  'attention; the optimize mode needs visdom tooling)' % options.mode)
