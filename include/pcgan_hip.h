@@ -697,6 +697,32 @@ int pcgan_gradcam_map(const void* act, const void* grad, float* map, int N, int 
 int pcgan_heatmap_overlay(const float* map, const void* img, const float* mean, const float* std, float alpha, float* out, float* lohi,
                           int N, int Cm, int H, int W, int dtype, pcgan_stream_t s);
 
+/* ---- online pair selection + draw-aware BCE of siamese_online.py (csrc/online_pair.hip) ---------------------------------------------------
+ * What the reference's online trainer does between the encoder's forward pass and backward().  Replaces
+ *   EmbeddingDistancePairSelector.get_pairs (three .cpu() copies, numpy argsort, LongTensor, .cuda())        siamese_online.py:218-265
+ *   OnlineBinaryCrossEntropyLoss.__call__ (LUT[label], index, two logsigmoid, mean)                          siamese_online.py:324-342
+ *   get_prediction (sigmoid, the draw band, the compares; stats.mode over one element is the identity)       siamese_online.py:385-394
+ *   (feat1.pow(2).mean() + feat2.pow(2).mean()) * lambda_regularization                                      siamese_online.py:630-635
+ * and their backward pass, in ONE launch of ONE workgroup: no workspace, no atomics, every order fixed, bit-identical from run to run.
+ * f1, f2: [N] fp32 ratings; label: [N] int64 in 0 .. 2 (clamped to that range); key: [N] fp32 or NULL.  1 <= N <= 4096, 1 <= k <= N.
+ *   s[n]      = f1[n] - f2[n] (fp32);  key[n] = s[n] * s[n] (fp32, the bits of the reference's (A - B).pow(2)) unless key is given
+ *   order     ascending by key, equal keys by ascending index (stable), -0 == +0, NaN after +inf (numpy's order); descending != 0 is the
+ *             exact reverse of that list (the reference's [::-1]), so equal keys then come with the higher index first
+ *   sel       the first k of the order;  pseudo: the last k, in list order (they overlap when 2 k > N)
+ *   target    t[n] = (1, 0.5, 0)[label[n]]: LABEL 0 MEANS "THE FIRST RATES HIGHER" -- the reverse of siamese.py's BinaryNLLLoss (0, 0.5, 1)
+ *   loss[0]   = (1 / k) sum over sel of -(t logsigmoid(s) + (1 - t) logsigmoid(-s)),  logsigmoid(x) = min(x, 0) - log1p(exp(-|x|))
+ *   loss[1]   = lambda_reg (mean(f1^2) + mean(f2^2))  (0 for lambda_reg == 0);   loss[2] = loss[0] + loss[1]
+ *             float64 from the fp32 inputs, each sum in ascending pair index, each of the three rounded to fp32 once
+ *   df1[n]    = gscale ( [n in sel] (sigmoid(s) - t) / k + lambda_reg 2 f1[n] / N )       float64, rounded once; ALL N always written
+ *   df2[n]    = gscale (-[n in sel] (sigmoid(s) - t) / k + lambda_reg 2 f2[n] / N )
+ *   picks     int32 [2 k + N]: sel, pseudo, pred[N];  with p = sigmoid(s) in float64: pred = 1 if |0.5 - p| < draw_thresh, else 0 if
+ *             p > 0.5, else 2 (get_prediction with ~idx1 for the `1 - idx1` current torch refuses on bool tensors)
+ * draw_thresh, lambda_reg and gscale are fp32 values widened to float64 exactly.  loss, df1, df2 and picks may each be NULL (not wanted).
+ * N or k out of range and a null f1 / f2 / label are reported before any launch. */
+int pcgan_online_pair_bce(const float* f1, const float* f2, const int64_t* label, const float* key, float* loss, float* df1, float* df2,
+                          int32_t* picks, int N, int k, int descending, float draw_thresh, float lambda_reg, float gscale,
+                          pcgan_stream_t s);
+
 /* ---- history of generated images (csrc/image_pool.hip) -----------------------------------------------------------------------------------
  * The call site it replaces is the per-image unsqueeze / clone / cat loop of the reference's ImagePool.query, util/image_pool.py:12-32.
  * x and y hold n_img images of n elements of `dtype` (PCGAN_F32 or PCGAN_BF16), pool holds pool_size such images; all contiguous.  plan

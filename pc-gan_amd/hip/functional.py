@@ -784,6 +784,46 @@ def pooled_mse(x, target, delta, is_max):
     return _PooledMseFn.apply(x, target, float(delta), bool(is_max))
 
 
+# ---------------------------------------------------------------------------- online pair selection + BCE (siamese_online.py)
+class _OnlinePairBceFn(torch.autograd.Function):
+    """pair selection + draw-aware BCE + rating regularizer + predictions as ONE node (pcgan_online_pair_bce): the forward launch leaves
+    d loss3[2] / d f1 and / d f2 behind, so backward launches nothing when the incoming factor is unit_gradient() and one pcgan_scale per
+    rating otherwise.  Only `total` (= loss3[2]) carries the graph; loss3 and picks are by-products for the caller's log and file."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, label, k, descending, draw_thresh, lambda_reg, key):
+        f1, f2 = _c(f1), _c(f2)
+        want = f1.requires_grad or f2.requires_grad
+        loss3, picks, df1, df2 = ops.online_pair_bce(f1, f2, _c(label), k, descending, draw_thresh, lambda_reg, 1.0,
+                                                     None if key is None else _c(key), want)
+        # loss3[2] as an output of its own over the same storage (no launch, and no view relation for autograd to track)
+        total = torch.empty((0,), dtype=torch.float32, device=loss3.device).set_(loss3.untyped_storage(), loss3.storage_offset() + 2, (), ())
+        ctx.save_for_backward(df1, df2)
+        ctx.mark_non_differentiable(loss3, picks)
+        ctx.set_materialize_grads(False)
+        return total, loss3, picks
+
+    @staticmethod
+    def backward(ctx, dtotal, *unused):
+        df1, df2 = ctx.saved_tensors
+        none = (None,) * 6
+        if df1 is None or dtotal is None:
+            return (None, None) + none
+        unit = _UNIT.get(dtotal.device)
+        if unit is not None and dtotal.data_ptr() == unit.data_ptr():
+            return (df1, df2) + none
+        factor = _c(dtotal).to(torch.float32).reshape(1)
+        return (ops.scale(df1, factor) if ctx.needs_input_grad[0] else None,
+                ops.scale(df2, factor) if ctx.needs_input_grad[1] else None) + none
+
+
+def online_pair_bce(f1, f2, label, k, descending, draw_thresh, lambda_reg=0.0, key=None):
+    """(total, loss3, picks) of the online trainer's loss on the ratings f1, f2 (any shape with N elements) and the int64 labels (0: the
+    first rates higher): loss3 = (bce over the k kept pairs, regularizer, sum), total = loss3[2] with the graph attached, picks = (sel[k],
+    pseudo[k], pred[N]) int32 -- see ops.online_pair_bce"""
+    return _OnlinePairBceFn.apply(f1, f2, label, int(k), bool(descending), float(draw_thresh), float(lambda_reg), key)
+
+
 # ---------------------------------------------------------------------------- projection discriminator head
 class _ProjectionHeadFn(torch.autograd.Function):
     """The head of NLayerProjectionDiscriminator (reference models/networks.py:830-838) as ONE node: pcgan_proj_head_fwd leaves the plane

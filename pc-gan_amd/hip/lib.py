@@ -193,6 +193,7 @@ SIGNATURES = {
     'pcgan_pool_exchange_launches': (ctypes.c_ulonglong, []),
     'pcgan_gradcam_map': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'pcgan_heatmap_overlay': (_i, [_vp, _vp, ctypes.POINTER(_f), ctypes.POINTER(_f), _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'pcgan_online_pair_bce': (_i, [_vp] * 8 + [_i, _i, _i, _f, _f, _f, _vp]),
 }
 
 _lib = None

@@ -1555,6 +1555,36 @@ def pool_mse_fwd(x, target, delta, is_max, gscale=1.0, want_grad=True):
     return loss, pred, hits, dx, arg
 
 
+# ---------------------------------------------------------------- online pair selection + BCE (csrc/online_pair.hip)
+ONLINE_PAIR_MAX = 4096
+
+
+def online_pair_bce(f1, f2, label, k, descending, draw_thresh, lambda_reg, gscale=1.0, key=None, want_grad=True):
+    """(loss3, picks, df1, df2) of the online pair selection + draw-aware BCE + rating regularizer through pcgan_online_pair_bce, one
+    launch (reference siamese_online.py:218-265, 324-342, 385-394, 630-635): f1, f2 the N fp32 ratings of the batch in any shape, label N
+    int64 values in 0 .. 2 (0: the FIRST rates higher), key N fp32 sort keys (None: (f1 - f2)^2).  loss3 = (bce over the k kept pairs,
+    regularizer, their sum) as 3 fp32; picks = (sel[k], pseudo[k], pred[N]) as 2 k + N int32; df = gscale d loss3[2] / d f in f's shape
+    (None unless want_grad) -- all on the device, nothing is read back."""
+    N = f1.numel()
+    for name, t in (('f2', f2), ('label', label), ('key', key)):
+        if t is not None and (t.numel() != N or t.device != f1.device):
+            raise RuntimeError('online_pair_bce: %s of shape %s on %s for %d ratings on %s' % (name, tuple(t.shape), t.device, N, f1.device))
+    _chk(f1, f2, key)
+    if label.dtype != torch.int64 or not label.is_contiguous():
+        raise RuntimeError('online_pair_bce: label must be a contiguous int64 tensor, got %s' % label.dtype)
+    k = int(k)
+    if not 1 <= N <= ONLINE_PAIR_MAX or not 1 <= k <= N:
+        raise RuntimeError('online_pair_bce: N %d, k %d outside 1 <= k <= N <= %d' % (N, k, ONLINE_PAIR_MAX))
+    loss = torch.empty((3,), dtype=torch.float32, device=f1.device)
+    picks = torch.empty((2 * k + N,), dtype=torch.int32, device=f1.device)
+    df1 = torch.empty_like(f1) if want_grad else None
+    df2 = torch.empty_like(f2) if want_grad else None
+    _L.check(_L.load().pcgan_online_pair_bce(_p(f1), _p(f2), _p(label), _p(key), _p(loss), _p(df1), _p(df2), _p(picks), N, k,
+                                             int(bool(descending)), float(draw_thresh), float(lambda_reg), float(gscale), _stream()),
+             'online_pair_bce')
+    return loss, picks, df1, df2
+
+
 # ---------------------------------------------------------------- projection discriminator head (csrc/proj_head.hip)
 def _proj_check(what, B, C, y, psi_w, psi_b, ly_w, ly_b):
     _chk(y, psi_w, psi_b, ly_w, ly_b)
