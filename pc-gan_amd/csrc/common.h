@@ -175,6 +175,61 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
     return r;
 }
 
+// block-wide float64 sum in a fixed order (blockDim.x = 64 WAVES): the wave butterfly, then the wave results in wave order through LDS;
+// scratch: WAVES doubles.  Result valid in all threads.
+template <int WAVES>
+__device__ __forceinline__ double block_sum_d(double v, double* scratch) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    v = wave_sum_d(v);
+    __syncthreads();
+    if (lane == 0) scratch[wave] = v;
+    __syncthreads();
+    double r = 0.0;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) r += scratch[i];
+    return r;
+}
+
+// ---- cross-workgroup finish: "the last arriving workgroup finishes the reduction", inside one launch ----------------------------------
+// Every workgroup publishes its partial result with WRITE-THROUGH stores (st_wt: agent-scope relaxed atomic stores = `global_store ...
+// sc1`), waits for them (s_waitcnt vmcnt(0)) and makes one returning agent-scope add on a ticket word; the workgroup whose add completes
+// the expected arrivals reads all the partials with ld_wt (sc1 loads: they bypass the non-coherent caches) and finishes in index order, so
+// the result does not depend on which workgroup is last.  Users: norm.hip (a ticket per channel: Chan merge / channel sums of train-mode
+// BatchNorm), linear_head.hip (loss, correct), pool_mse_head.hip (loss, hits).
+//  * No fences: a release fence per workgroup writes back the whole L2 of its XCD (MI355X_MICROARCH.md: 1.7 - 6.5 us each) -- the first
+//    version of the BatchNorm statistics kernel, with __threadfence(), made the step 2.7 ms SLOWER than the three-launch form it replaces.
+//  * The decision is old + 1 == arrivals, and the arrival that finds it puts the ticket back to 0 (an agent-scope atomic store, complete
+//    when the launch is).  It does not depend on the history of the ticket, so calls with DIFFERENT arrival counts may share one (the
+//    partial last batch of an epoch, test() and get_current_visuals() at another N, two heads on one workspace) and a captured hipGraph
+//    replays correctly.  Round 3's never-cleared form, (old + 1) % N == 0, picked a wrong last arriver for the rest of the run once a call
+//    with another N had moved the counter off a multiple of N.
+//  * The calls that share a ticket run in STREAM ORDER, so the reset of one launch is visible to the next (a BatchNorm net never runs two
+//    passes at once: its running statistics must stay ordered anyway; the heads' workspace is per stream).  The ticket is zero before the
+//    first call.
+//  * What a caller must keep (cdna_hip_programming.md, Guideline 16, checks 1 - 4): (1) every handed-off value is stored with st_wt;
+//    (2) the wave that stored them is the one that calls ticket_arrive, which drains its stores before the ticket moves (stores by other
+//    waves need their own s_waitcnt vmcnt(0) and a barrier in front); (3) the ticket is only ever written by the atomics below;
+//    (4) EVERY load of handed-off bytes in the finisher is an ld_wt -- one plain load can hit a stale line of this CU's L1.
+__device__ __forceinline__ void st_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_wt(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float ld_wt(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double ld_wt(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// ONE thread of the workgroup, after ITS st_wt stores of the partials: true if this arrival at tickets[slot] is the last of `arrivals`
+__device__ __forceinline__ bool ticket_arrive(unsigned* tickets, int slot, unsigned arrivals) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the write-through stores have left before the ticket moves
+    unsigned* ticket = &tickets[slot];
+    const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = (old + 1u) == arrivals;
+    if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return last;
+}
+// the workgroup form: thread 0 (which stored the partials) arrives at tickets[slot]; true in EVERY thread of the workgroup that arrived last
+__device__ __forceinline__ bool block_arrives_last(unsigned* tickets, int slot, unsigned arrivals, int* flag_lds) {
+    if (threadIdx.x == 0) *flag_lds = ticket_arrive(tickets, slot, arrivals);
+    __syncthreads();
+    return *flag_lds != 0;
+}
+
 // Two fp16 pieces, x * 2^e = h + l (11 + 11 significand bits), products (l,h) (h,l) (h,h): HALF the matrix instructions of the
 // three-piece bf16 split.  scripts/micro/bf16_split, K = 2304 against float64: relative L2 error 5.3e-7 (fp32 MFMA 6.1e-7, bf16 x 6
 // 7.0e-7).  fp16 has 5 exponent bits, so each operand tensor is scaled by a power of two that puts its largest magnitude in

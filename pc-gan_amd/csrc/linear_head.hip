@@ -9,18 +9,14 @@
 // 128-bit loads along c, wave64 shuffle reductions; the matrix pipe is not used.  Every sum runs in a fixed order in float64 (the sizes
 // are tiny: the launches are bound by latency, not by arithmetic) and is rounded to fp32 once, so results are bit-identical from run to run and carry one
 // rounding against exact arithmetic.  No float atomics.  The two batch-wide scalars of the forward pass (loss, correct) are finished by
-// the LAST ARRIVING workgroup of the same launch with norm.hip's ticket scheme: write-through stores of the row partials, s_waitcnt, one
-// returning agent-scope integer add on the ticket, sc1 loads in the finisher, which sums the rows in index order (the result does not
-// depend on which workgroup is last) and puts the ticket back to 0.
+// the LAST ARRIVING workgroup of the same launch, which sums the row partials in index order (common.h, "cross-workgroup finish").
 #include "common.h"
 
 namespace pcgan {
 
 static constexpr int LH_THREADS = 256;
+static constexpr int LH_WAVES = LH_THREADS / 64;
 static constexpr int LH_MAX_N = 512, LH_MAX_C = 2048, LH_MAX_K = 1024;
-
-__device__ __forceinline__ void lh_st_wt(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double lh_ld_wt(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // four consecutive floats: one 16-byte access when the tensor allows it (vec), else four 4-byte ones
 __device__ __forceinline__ float4 lh_ld4(const float* p, int vec) {
@@ -33,19 +29,6 @@ __device__ __forceinline__ void lh_st4(float* p, const float4& v, int vec) {
     } else {
         p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
     }
-}
-
-// block-wide float64 sum in a fixed order (blockDim.x = LH_THREADS); valid in every thread
-__device__ __forceinline__ double lh_block_sum(double v, double* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum_d(v);
-    __syncthreads();
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < LH_THREADS / 64; ++i) r += scratch[i];
-    return r;
 }
 
 // workspace layout (doubles): [0] the ticket word (an unsigned in the first 4 bytes), [1 .. N] weighted row losses, [N + 1 .. 2 N] row hits
@@ -62,7 +45,7 @@ struct LinearCeArgs {
 __global__ void __launch_bounds__(LH_THREADS) linear_ce_fwd_kernel(const LinearCeArgs a) {
     __shared__ float xs[LH_MAX_C];
     __shared__ double lg[LH_MAX_K];
-    __shared__ double scratch[LH_THREADS / 64];
+    __shared__ double scratch[LH_WAVES];
     __shared__ double bmax;
     __shared__ int barg;
     __shared__ int last_flag;
@@ -75,7 +58,7 @@ __global__ void __launch_bounds__(LH_THREADS) linear_ce_fwd_kernel(const LinearC
         const long long yi = a.y[i];
         if (yi >= 0 && yi < K) wpart += a.wt ? (double)a.wt[yi] : 1.0;
     }
-    const double wsum = lh_block_sum(wpart, scratch);
+    const double wsum = block_sum_d<LH_WAVES>(wpart, scratch);
 
     const float* xr = a.x + (size_t)n * C;
     for (int i = tid; i < C4; i += LH_THREADS) {
@@ -84,7 +67,7 @@ __global__ void __launch_bounds__(LH_THREADS) linear_ce_fwd_kernel(const LinearC
     }
     __syncthreads();
     // one wave per class: lanes stride over c, float64 partial sums, xor-shuffle tree
-    for (int k = wave; k < K; k += LH_THREADS / 64) {
+    for (int k = wave; k < K; k += LH_WAVES) {
         const float* wr = a.w + (size_t)k * C;
         double s = 0.0;
         for (int i = lane; i < C4; i += 64) {
@@ -121,7 +104,7 @@ __global__ void __launch_bounds__(LH_THREADS) linear_ce_fwd_kernel(const LinearC
     const double mx = bmax;
     double epart = 0.0;
     for (int k = tid; k < K; k += LH_THREADS) epart += exp(lg[k] - mx);
-    const double esum = lh_block_sum(epart, scratch);
+    const double esum = block_sum_d<LH_WAVES>(epart, scratch);
     const long long yn = a.y[n];
     const bool valid = yn >= 0 && yn < K;          // a label outside [0, K) is an ignored row: weight 0, no table look-up
     const double wy = valid ? (a.wt ? (double)a.wt[yn] : 1.0) : 0.0;
@@ -135,24 +118,19 @@ __global__ void __launch_bounds__(LH_THREADS) linear_ce_fwd_kernel(const LinearC
     if (tid == 0) {
         const double row_loss = valid ? wy * (log(esum) - (lg[yn] - mx)) : 0.0;
         if (a.pred) a.pred[n] = barg;
-        lh_st_wt(a.ws + 1 + n, row_loss);
-        lh_st_wt(a.ws + 1 + a.N + n, (valid && (long long)barg == yn) ? 1.0 : 0.0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the write-through stores have left before the ticket moves
-        unsigned* ticket = reinterpret_cast<unsigned*>(a.ws);
-        const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = (old + 1u) == (unsigned)a.N;
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = last;
+        st_wt(a.ws + 1 + n, row_loss);
+        st_wt(a.ws + 1 + a.N + n, (valid && (long long)barg == yn) ? 1.0 : 0.0);
+        last_flag = ticket_arrive(reinterpret_cast<unsigned*>(a.ws), 0, (unsigned)a.N);
     }
     __syncthreads();
     if (!last_flag) return;
     double lpart = 0.0, hpart = 0.0;
     for (int i = tid; i < a.N; i += LH_THREADS) {
-        lpart += lh_ld_wt(a.ws + 1 + i);
-        hpart += lh_ld_wt(a.ws + 1 + a.N + i);
+        lpart += ld_wt(a.ws + 1 + i);
+        hpart += ld_wt(a.ws + 1 + a.N + i);
     }
-    const double lsum = lh_block_sum(lpart, scratch);
-    const double hsum = lh_block_sum(hpart, scratch);
+    const double lsum = block_sum_d<LH_WAVES>(lpart, scratch);
+    const double hsum = block_sum_d<LH_WAVES>(hpart, scratch);
     if (tid == 0) {
         if (a.loss) a.loss[0] = (float)(lsum / wsum);
         if (a.correct) a.correct[0] = (int)hsum;

@@ -15,38 +15,13 @@
 namespace pcgan {
 
 // ---- "last arriver finishes the channel": the batch-norm reductions over the N planes of a channel without a second launch ----------
-// The per-plane kernels below (one workgroup per (n, c) plane) can be given a ticket word per channel.  Every workgroup publishes its
-// plane's partial result with WRITE-THROUGH stores (agent-scope relaxed atomic stores = `global_store ... sc1`), waits for them
-// (s_waitcnt vmcnt(0)) and makes one returning agent-scope atomicAdd on ticket[c]; the workgroup whose add completes the channel's N
-// arrivals reads the partials with sc1 loads (they bypass the non-coherent caches) and finishes the channel with the arithmetic of the
-// stand-alone merge kernels (same order: the result does not depend on which workgroup is last).  No fences: a release fence per
-// workgroup writes back the whole L2 of its XCD (MI355X_MICROARCH.md: 1.7 - 6.5 us each) -- the first version of this kernel with
-// __threadfence() made the step 2.7 ms SLOWER than the three-launch form it replaces.  The arrival that finds old + 1 == N is the last
-// of its call and puts the ticket back to 0 (an agent-scope atomic store, complete when the launch is): the decision does not depend on
-// the history of the ticket array, so calls with DIFFERENT batch sizes may share it (the partial last batch of an epoch, test() and
-// get_current_visuals() at another N: round 3's never-cleared form, (old + 1) % N == 0, picked a wrong last arriver for the rest of the
-// run once a call with another N had moved the counter off a multiple of N) and a captured hipGraph replays correctly; the calls that
-// share a ticket array run in stream order (a BatchNorm net never runs two passes at once: its running statistics must stay ordered
-// anyway), so the reset of one launch is visible to the next.
+// The per-plane kernels below (one workgroup per (n, c) plane) can be given a ticket word per channel: thread 0 stores the plane's
+// partial result with st_wt, and the workgroup whose arrival completes the channel's N finishes the channel with the arithmetic of the
+// stand-alone merge kernels.  The protocol and its conditions: common.h, "cross-workgroup finish".
 struct BnTicket {
     unsigned* ticket;       // [C] arrival counters of this layer and pass direction, or null: no merge in this launch
     int N, C;
 };
-// true in every thread of the workgroup that completed channel c (call after the plane's partials were stored by thread 0)
-__device__ __forceinline__ void st_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_wt(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// call with the plane's partials already stored by thread 0 through st_wt
-__device__ __forceinline__ bool bn_last_arriver(const BnTicket& t, int c, int* flag_lds) {
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the write-through stores have left before the ticket moves
-        const unsigned old = __hip_atomic_fetch_add(&t.ticket[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = (old + 1u) == (unsigned)t.N;
-        if (last) __hip_atomic_store(&t.ticket[c], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag_lds = last;
-    }
-    __syncthreads();
-    return *flag_lds != 0;
-}
 // Chan merge of the N plane statistics of channel c by ONE wave (lane = threadIdx.x < 64): the arithmetic of bn_merge_kernel
 template <bool WT>      // WT: the partials were published by other workgroups of THIS launch (sc1 loads); else by an earlier launch
 __device__ __forceinline__ void bn_merge_channel(const float* mean_nc, const float* m2_nc, float* __restrict__ mean_c,
@@ -155,7 +130,7 @@ __global__ void __launch_bounds__(256) plane_stats_kernel(const T* __restrict__ 
     if (tk.ticket != nullptr) {      // batch norm: the workgroup that completes its channel merges the N plane statistics (bn_merge_kernel)
         __shared__ int last_flag;
         const int c = (int)(plane % (size_t)tk.C);
-        if (bn_last_arriver(tk, c, &last_flag) && threadIdx.x < 64) {
+        if (block_arrives_last(tk.ticket, c, (unsigned)tk.N, &last_flag) && threadIdx.x < 64) {
             bn_merge_channel<true>(mean_nc, m2_nc, mo.mean_c, mo.var_c, mo.running_mean, mo.running_var, tk.N, tk.C, HW, mo.momentum, c, threadIdx.x);
             if (c == 0 && threadIdx.x == 0 && mo.batches) mo.batches[0] += 1;       // num_batches_tracked: once per call
         }
@@ -293,7 +268,7 @@ __global__ void __launch_bounds__(256) norm_bwd_stats_kernel(NormArgs a, BnTicke
     if (tk.ticket != nullptr) {      // batch norm: the last arriver sums the channel's N plane sums (bn_bwd_reduce_kernel)
         __shared__ int last_flag;
         const int c = (int)(plane % (size_t)tk.C);
-        if (bn_last_arriver(tk, c, &last_flag) && threadIdx.x < 64)
+        if (block_arrives_last(tk.ticket, c, (unsigned)tk.N, &last_flag) && threadIdx.x < 64)
             bn_sum_channel<true>((const float*)a.out, (const float*)a.out2, s1_c, s2_c, tk.N, tk.C, c, threadIdx.x);
     }
 }

@@ -13,36 +13,19 @@
 // back coalesced.  Longer planes (must be correct, need not be fast) take one workgroup per plane.
 //
 // Every sum runs in a fixed order in float64 and is rounded to fp32 once; no float atomics: results are bit-identical from run to run.
-// The two batch-wide scalars (loss, hits) are finished by the LAST ARRIVING workgroup of the same launch with norm.hip's ticket scheme,
-// as in linear_head.hip: write-through stores of the workgroup partials, s_waitcnt, one returning agent-scope integer add on the ticket,
-// sc1 loads in the finisher, which sums the partials by index (the result does not depend on which workgroup is last) and puts the
-// ticket back to 0.
+// The two batch-wide scalars (loss, hits) are finished by the LAST ARRIVING workgroup of the same launch, which sums the workgroup
+// partials by index (common.h, "cross-workgroup finish").
 #include <float.h>
 #include "common.h"
 
 namespace pcgan {
 
 static constexpr int PM_THREADS = 256;
+static constexpr int PM_WAVES = PM_THREADS / 64;
 static constexpr int PM_PLANES = 128;          // planes per workgroup on the staged path (64: 17.6 us against 13.9 us at 51 200 planes)
 static constexpr int PM_SHORT = 64;            // longest plane of the staged path
 static constexpr int PM_LD1 = PM_PLANES * PM_SHORT / PM_THREADS, PM_LD4 = PM_LD1 / 4;      // loads per thread: elements, groups of four
 static constexpr int PM_MAX_NF = 1 << 22, PM_MAX_HW = 1 << 20;
-
-__device__ __forceinline__ void pm_st_wt(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double pm_ld_wt(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// block-wide float64 sum in a fixed order (blockDim.x = PM_THREADS); valid in every thread
-__device__ __forceinline__ double pm_block_sum(double v, double* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum_d(v);
-    __syncthreads();
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < PM_THREADS / 64; ++i) r += scratch[i];
-    return r;
-}
 
 // workspace layout (doubles): [0] the ticket word (an unsigned in the first 4 bytes), [1 .. B] squared-error sums of the B workgroups,
 // [B + 1 .. 2 B] their hit counts
@@ -76,24 +59,19 @@ __device__ __forceinline__ float pm_plane(const PoolMseArgs& a, int plane, float
 __device__ __forceinline__ void pm_finish(const PoolMseArgs& a, double bsq, double bhit, double* scratch, int* last_flag) {
     const int tid = threadIdx.x, B = gridDim.x;
     if (tid == 0) {
-        pm_st_wt(a.ws + 1 + blockIdx.x, bsq);
-        pm_st_wt(a.ws + 1 + B + blockIdx.x, bhit);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the write-through stores have left before the ticket moves
-        unsigned* ticket = reinterpret_cast<unsigned*>(a.ws);
-        const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = (old + 1u) == (unsigned)B;
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *last_flag = last;
+        st_wt(a.ws + 1 + blockIdx.x, bsq);
+        st_wt(a.ws + 1 + B + blockIdx.x, bhit);
+        *last_flag = ticket_arrive(reinterpret_cast<unsigned*>(a.ws), 0, (unsigned)B);
     }
     __syncthreads();
     if (!*last_flag) return;
     double lpart = 0.0, hpart = 0.0;
     for (int i = tid; i < B; i += PM_THREADS) {
-        lpart += pm_ld_wt(a.ws + 1 + i);
-        hpart += pm_ld_wt(a.ws + 1 + B + i);
+        lpart += ld_wt(a.ws + 1 + i);
+        hpart += ld_wt(a.ws + 1 + B + i);
     }
-    const double lsum = pm_block_sum(lpart, scratch);
-    const double hsum = pm_block_sum(hpart, scratch);
+    const double lsum = block_sum_d<PM_WAVES>(lpart, scratch);
+    const double hsum = block_sum_d<PM_WAVES>(hpart, scratch);
     if (tid == 0) {
         if (a.loss) a.loss[0] = (float)(lsum / (double)a.NF);
         if (a.hits) a.hits[0] = (int)hsum;
@@ -106,7 +84,7 @@ __global__ void __launch_bounds__(PM_THREADS) pool_mse_short_kernel(const PoolMs
     __shared__ float xs[PM_PLANES * (PM_SHORT + 1)];
     __shared__ float gs[PM_PLANES];
     __shared__ int as[PM_PLANES];
-    __shared__ double scratch[PM_THREADS / 64];
+    __shared__ double scratch[PM_WAVES];
     __shared__ int last_flag;
     const int tid = threadIdx.x, HW = a.HW;
     const int p0 = blockIdx.x * PM_PLANES;
@@ -193,17 +171,17 @@ __global__ void __launch_bounds__(PM_THREADS) pool_mse_short_kernel(const PoolMs
             st1(db + e, (!is_max || i == as[pl]) ? gs[pl] : 0.f);
         }
     }
-    const double bsq = pm_block_sum(sq, scratch);
-    const double bhit = pm_block_sum(hit, scratch);
+    const double bsq = block_sum_d<PM_WAVES>(sq, scratch);
+    const double bhit = block_sum_d<PM_WAVES>(hit, scratch);
     pm_finish(a, bsq, bhit, scratch, &last_flag);
 }
 
 // HW > PM_SHORT: one workgroup per plane, threads stride over the plane
 template <typename T>
 __global__ void __launch_bounds__(PM_THREADS) pool_mse_long_kernel(const PoolMseArgs a) {
-    __shared__ double scratch[PM_THREADS / 64];
-    __shared__ float wbest[PM_THREADS / 64];
-    __shared__ int warg[PM_THREADS / 64];
+    __shared__ double scratch[PM_WAVES];
+    __shared__ float wbest[PM_WAVES];
+    __shared__ int warg[PM_WAVES];
     __shared__ float g_sh;
     __shared__ int arg_sh;
     __shared__ int last_flag;
@@ -230,13 +208,13 @@ __global__ void __launch_bounds__(PM_THREADS) pool_mse_long_kernel(const PoolMse
         if (tid == 0) {
             pr = wbest[0];
             arg = warg[0];                                      // wave 0 holds element 0: never the sentinel
-            for (int w = 1; w < PM_THREADS / 64; ++w)
+            for (int w = 1; w < PM_WAVES; ++w)
                 if (warg[w] != 0x7fffffff && (wbest[w] > pr || (wbest[w] == pr && warg[w] < arg))) { pr = wbest[w]; arg = warg[w]; }
         }
     } else {
         double s = 0.0;
         for (int i = tid; i < HW; i += PM_THREADS) s += (double)ld1(xp + i);
-        s = pm_block_sum(s, scratch);
+        s = block_sum_d<PM_WAVES>(s, scratch);
         pr = (float)(s / (double)HW);
     }
     double sq = 0.0, hit = 0.0;

@@ -75,19 +75,6 @@ __device__ __forceinline__ void ph_store(bf16* p, const float (&v)[8], int vec) 
     }
 }
 
-// block-wide float64 sum in a fixed order (blockDim.x = PH_THREADS); valid in every thread
-__device__ __forceinline__ double ph_block_sum(double v, double* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum_d(v);
-    __syncthreads();
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < PH_WAVES; ++i) r += scratch[i];
-    return r;
-}
-
 // ---- forward, launch 1: h[plane] = sum of the plane -------------------------------------------------------------------------------
 // A thread's elements ascend, so the plane they belong to never decreases: it keeps one running sum, and files it in its own column of
 // part[plane][thread] when the plane changes (each slot is written at most once; the others stay 0).  A plane's sum is then the sum of
@@ -165,8 +152,8 @@ __device__ __forceinline__ void ph_row_logits(const ProjRowArgs& a, int b, const
         s += hh * ph_wy(a.ly_w, a.ly_b, yv, c, a.nz);
         t += hh * (double)a.psi_w[c];
     }
-    s = ph_block_sum(s, scratch);
-    t = ph_block_sum(t, scratch);
+    s = block_sum_d<PH_WAVES>(s, scratch);
+    t = block_sum_d<PH_WAVES>(t, scratch);
     border = s + (double)a.psi_b[0];
     centre = border + t;
 }

@@ -1458,16 +1458,19 @@ def global_pool_bwd(dy, arg, in_hw, is_max):
 
 
 # ---------------------------------------------------------------- classifier head, training pass (csrc/linear_head.hip)
-_CE_WS = {}
+_HEAD_WS = {}
 
 
-def _ce_workspace(device, nbytes):
-    """the forward call's workspace, one per (device, stream): its first word is the kernel's arrival ticket, zero before the first call
-    and left zero by every call (include/pcgan_hip.h), so it is allocated zeroed once and grown zeroed"""
-    key = (device, _raw_stream())
-    ws = _CE_WS.get(key)
+def _head_workspace(pool, device, nbytes, zeroed):
+    """the float64 workspace of a head kernel: one per (pool, device, stream), grown on demand, shared by the calls of its pool in stream
+    order.  zeroed: the first word is a kernel's arrival ticket, zero before the first call and left zero by every call
+    (include/pcgan_hip.h; csrc/common.h, "cross-workgroup finish"), so the buffer is allocated zeroed once and grown zeroed -- pool
+    'finish', shared by linear_ce_fwd and pool_mse_fwd.  Not zeroed: the buffer carries values from a call's first launch to its second and
+    no state between calls -- pool 'proj'."""
+    key = (pool, device, _raw_stream())
+    ws = _HEAD_WS.get(key)
     if ws is None or ws.numel() * 8 < nbytes:
-        ws = _CE_WS[key] = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=device)
+        ws = _HEAD_WS[key] = (torch.zeros if zeroed else torch.empty)((nbytes + 7) // 8, dtype=torch.float64, device=device)
     return ws
 
 
@@ -1495,7 +1498,7 @@ def linear_ce_fwd(x, w, b, labels, class_weight=None, want_grad=True):
         raise RuntimeError('linear_ce_fwd: class_weight of shape %s for %d classes' % (tuple(class_weight.shape), K))
     lib = _L.load()
     nbytes = lib.pcgan_linear_ce_workspace_bytes(N)
-    ws = _ce_workspace(x.device, nbytes) if nbytes else None
+    ws = _head_workspace('finish', x.device, nbytes, True) if nbytes else None
     loss = torch.empty((), dtype=torch.float32, device=x.device)
     logits = torch.empty((N, K), dtype=torch.float32, device=x.device)
     dlogits = torch.empty_like(logits) if want_grad else None
@@ -1544,7 +1547,7 @@ def pool_mse_fwd(x, target, delta, is_max, gscale=1.0, want_grad=True):
                            % (tuple(target.shape), target.device, N, F, x.device))
     lib = _L.load()
     nbytes = lib.pcgan_pool_mse_workspace_bytes(N * F)
-    ws = _ce_workspace(x.device, nbytes) if nbytes else None
+    ws = _head_workspace('finish', x.device, nbytes, True) if nbytes else None
     loss = torch.empty((), dtype=torch.float32, device=x.device)
     pred = torch.empty((N, F, 1, 1), dtype=torch.float32, device=x.device)
     hits = torch.empty((), dtype=torch.int32, device=x.device)
@@ -1597,19 +1600,6 @@ def _proj_check(what, B, C, y, psi_w, psi_b, ly_w, ly_b):
     return By, nz
 
 
-_PROJ_WS = {}
-
-
-def _proj_workspace(device, nbytes):
-    """the backward call's workspace, one per (device, stream), grown on demand: it carries values from the call's first launch to its
-    second and no state between calls, so calls in stream order share it"""
-    key = (device, _raw_stream())
-    ws = _PROJ_WS.get(key)
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = _PROJ_WS[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    return ws
-
-
 def proj_head_fwd(p, y, psi_w, psi_b, ly_w, ly_b, sigmoid):
     """(out, h) of the projection discriminator's head through pcgan_proj_head_fwd: p (B, C, H, W) fp32 or bf16, y (By, nz) fp32 with
     By in {1, B}, psi.weight (1, C, 1, 1), psi.bias (1,), l_y.weight (C, nz, 1, 1), l_y.bias (C,).  out is (B, 1, 3, 3) in p's storage
@@ -1655,7 +1645,7 @@ def proj_head_bwd(g, h, y, psi_w, psi_b, ly_w, ly_b, in_hw, sigmoid, want_dp=Tru
     dy = torch.empty((By, nz), dtype=torch.float32, device=g.device) if want_dy else None
     lib = _L.load()
     nbytes = lib.pcgan_proj_head_bwd_workspace_bytes(B, nz)
-    ws = _proj_workspace(g.device, nbytes)
+    ws = _head_workspace('proj', g.device, nbytes, False)
     _L.check(lib.pcgan_proj_head_bwd(_p(g), _p(h), _p(y), _p(psi_w), _p(psi_b), _p(ly_w), _p(ly_b), _p(dp), _p(grads[0]), _p(grads[1]),
                                      _p(grads[2]), _p(grads[3]), _p(dy), _p(ws), nbytes, B, C, H * W, nz, By, int(bool(sigmoid)), int(acc),
                                      dt, _stream()), 'proj_head_bwd')

@@ -204,6 +204,48 @@ def test_rows_with_a_label_outside_the_classes_are_ignored(dev):
     assert bool(torch.isnan(loss)), 'all rows ignored: 0 / 0, as torch'
 
 
+def test_both_heads_at_changing_sizes_on_the_one_workspace(dev):
+    """ops hands linear_ce_fwd and pool_mse_fwd the same ticketed workspace: calls of changing N, of both heads, in stream order, each
+    held to float64 as the tests of its own kernel hold it; every call leaves the ticket word zero.  The last classifier call was asked
+    for at (N, C, K) = (4, 6, 2), which the kernel's contract refuses (C a multiple of 4, include/pcgan_hip.h): that refusal is asserted,
+    before any launch, and the call is made at (4, 4, 2) -- the ticket sees N, which is what changes"""
+    from pcgan_amd.hip import ops
+    import test_gpu_regression as TR
+    calls = []
+    for i, shape in enumerate(((5, 8, 3), (3, 8, 3), (5, 8, 3), (3, 2, 50), (4, 4, 2))):
+        if i == 4:
+            x, w, b, y, wt = _head_case(4, 6, 2, 94, True)
+            with pytest.raises(RuntimeError, match='multiple of 4'):
+                ops.linear_ce_fwd(x.to(dev), w.to(dev), b.to(dev), y.to(dev), wt.to(dev))
+        if i == 3:
+            x, t = TR._case(*shape, False, 41, False)
+            calls.append((shape, (x, t), ops.pool_mse_fwd(x.to(dev), t.to(dev), TR.DELTA, False)))
+        else:
+            x, w, b, y, wt = _head_case(*shape, 90 + i, True)
+            calls.append((shape, (x, w, b, y, wt), ops.linear_ce_fwd(x.to(dev), w.to(dev), b.to(dev), y.to(dev), wt.to(dev))))
+    torch.cuda.synchronize()
+    for i, (shape, args, out) in enumerate(calls):
+        what = 'call %d %s' % (i, shape)
+        if i == 3:
+            x, t = args
+            r32, r64 = TR._torch_ref(x, t, False, 1.0, torch.float32), TR._torch_ref(x, t, False, 1.0, torch.float64)
+            loss, pred, hits, dx, arg = out
+            for k, v in dict(pred=pred, loss=loss.reshape(1), dx=dx).items():
+                TR._held(v, r32[k], r64[k], '%s: %s' % (what, k))
+            assert arg is None and int(hits) == int((torch.abs(pred.cpu() - t.view_as(pred)) < TR.DELTA).sum()), what
+        else:
+            x, w, b, y, wt = args
+            r32, r64 = _torch_head(x, w, b, y, wt, torch.float32), _torch_head(x, w, b, y, wt, torch.float64)
+            loss, logits, dlogits, pred, correct = out
+            for k, v in dict(logits=logits, loss=loss.reshape(1), dlogits=dlogits).items():
+                _held(v, r32[k], r64[k], '%s: %s' % (what, k))
+            assert pred.cpu().tolist() == logits.cpu().numpy().argmax(axis=1).tolist(), what
+            assert int(correct) == int((pred.cpu() == y).sum()), what
+    ws = ops._head_workspace('finish', calls[0][2][0].device, 8, True)
+    assert ws.numel() >= 1 + 2 * 6, 'the pool the calls above used, not a new one'
+    assert ws.view(torch.int32)[:2].tolist() == [0, 0], 'the ticket is left zero'
+
+
 # ---- the whole classifier, one training step -------------------------------------------------------------------------------------------
 # (trunk, image size, weight seed, output tolerance): 64 -> a 2 x 2 last feature map (5e-4, as the encoder test), 96 -> 3 x 3, 128 -> 4 x 4.
 # Weights: test_gpu_inception_score._random_resnet_sd (the norms that end a residual branch are scaled down, so activations stay O(1)
