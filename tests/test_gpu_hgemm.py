@@ -10,7 +10,7 @@ after the library's clamps -- every case below asserts that record, so a test ca
 Calls go through ops.conv2d_fwd / ops.conv2d_bwd_data with a pack cache (the production path); the reference is oracle.ops_ref.conv2d in
 float64.  Bounds (fp32 tensors): relative L2 error < 3e-6 and < 2 x that of the fp32 MFMA kernels + 5e-7, and
 max |error| <= 2e-5 of the largest reference magnitude (one wrong edge pixel cannot hide under the norm).  bf16 tensors: per element,
-see _bf16_bound."""
+see _bf16_bound.  The per-element and exact-piece cases of every instantiation are in tests/test_gpu_hgemm_cases.py."""
 import pytest
 import torch
 
