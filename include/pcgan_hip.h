@@ -775,6 +775,11 @@ int pcgan_set_nonfinite_counter(unsigned int* dev_word);
  *                      every kernel family, cut to [1, chunks of 32 pixels (strips)] and not held to the heuristic's 8-chunk floor; the
  *                      chunks of a split and the final count are re-derived as always, and the workspace query follows (tests:
  *                      tests/test_gpu_wgrad_generic.py; the host maps no environment variable onto it)
+ *   "hwgrad_ks"     0  pcgan_conv2d_bwd_weight_hsplit, per-tap kernel: 0 = the library's split heuristic; 1 .. 512 forces that many splits
+ *                      of the pixel reduction, cut to [1, stages of 16 output columns] and not held to the heuristic's 8-stage floor; the
+ *                      stages of a split and the final count are re-derived as always, and
+ *                      pcgan_conv2d_hsplit_wgrad_workspace_bytes follows (tests: tests/test_gpu_hsplit_wgrad_cases.py; the host maps no
+ *                      environment variable onto it)
  * Unknown keys / values return non-zero. */
 int pcgan_set_option(const char* key, int value);
 int pcgan_get_option(const char* key, int* value);
@@ -799,14 +804,24 @@ int pcgan_igemm_last_launch(int* info, int n);
  * gradient runs): which instantiation its last call launched, after every clamp of a forced "wgrad_ks".  info[0 .. n) = {sequence number
  * (+1 per recorded launch), family (PCGAN_WGRAD_*), padding mode (0 zero, 1 reflection), BM (0 for the small-M kernels), VECA (dY fetched
  * four pixels at a time; tile kernels only), variant (see the families), storage type (PCGAN_F32 / PCGAN_BF16), splits, units per split
- * (chunks of 32 pixels; strips for PCGAN_WGRAD_STRIP)}; entries past PCGAN_WGRAD_LAUNCH_INFO are 0.  The hsplit / bsplit / row-ring /
- * direct weight gradients do not record. */
+ * (chunks of 32 pixels; strips for PCGAN_WGRAD_STRIP)}; entries past PCGAN_WGRAD_LAUNCH_INFO are 0.  The per-tap (hsplit) weight gradient
+ * has a record of its own (pcgan_hwgrad_last_launch below); the bsplit / row-ring / direct weight gradients do not record. */
 #define PCGAN_WGRAD_LAUNCH_INFO 9
 #define PCGAN_WGRAD_TILE2 1   /* wgrad2_kernel (tap-aligned K tiles, pipelined); variant = taps per K tile, 2 | 1 */
 #define PCGAN_WGRAD_TILE 2    /* wgrad_kernel; variant = KMODE 0 (generic) | 1 (per-thread tap) | 2 (one tap per K tile) */
 #define PCGAN_WGRAD_SMALLM 3  /* smallm_wgrad_kernel (<= 4 output channels, multiple of 16 padded channels); variant 0 */
 #define PCGAN_WGRAD_STRIP 4   /* smallm_wgrad_strip_kernel (<= 3 output channels, stride 1); variant = NT 4 | 7 */
 int pcgan_wgrad_last_launch(int* info, int n);
+/* Launch record of the per-tap weight gradient (hsplit_wgrad_kernel; host memory, no synchronisation, a record of its own): written by
+ * pcgan_conv2d_bwd_weight_hsplit only when it issues the launch of the per-tap kernel itself (an attempted launch: the record is
+ * written before the launch status is read, as pcgan_wgrad_last_launch's is) -- a call it hands to the row-ring or direct form does
+ * not move it.  info[0 .. n) = {sequence number (+1 per recorded launch), BM (128 | 256), stride, storage type (PCGAN_F32 / PCGAN_BF16),
+ * columns per workgroup (128 | 256), form (0 separable gather of a padded copy or of an unpadded tensor, 1 reflection applied in the
+ * gather, 2 GEN: zero padding applied in the gather), padded copy (0 none, 1 made by the element-per-thread kernel, 2 by the
+ * wave-per-plane kernel), row tiles, column tiles, splits (after every clamp of a forced "hwgrad_ks"), stages per split, stages in all};
+ * entries past PCGAN_HWGRAD_LAUNCH_INFO are 0. */
+#define PCGAN_HWGRAD_LAUNCH_INFO 12
+int pcgan_hwgrad_last_launch(int* info, int n);
 
 #ifdef __cplusplus
 }

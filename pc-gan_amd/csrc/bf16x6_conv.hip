@@ -11,6 +11,8 @@
 // What bounds them: DESIGN.md sections 3 and 8.  Reference call sites replaced: see include/pcgan_hip.h and the kernel units.
 #include "bsplit.h"
 
+#include <mutex>
+
 namespace pcgan {
 
 // M tile: 256 rows (8 waves share one gathered pixel tile) when the produced channels fill it, else 128
@@ -356,6 +358,9 @@ static inline int hsplit_wgrad_splits(const pcgan_conv_desc* d, int* nst_split) 
     long want = (hsplit_wgrad_bm(d) == 256 ? 256 : 512) / tiles;          // one round of resident workgroups
     if (want < 1) want = 1;
     if (want > nst / 8) want = nst / 8 > 0 ? nst / 8 : 1;
+    // option "hwgrad_ks" > 0 (tests): that many splits, cut to [1, stages]; the stages of a split and the final count are re-derived below
+    const int fk = option(OPT_HWGRAD_KS);
+    if (fk > 0) want = fk < nst ? fk : nst;
     *nst_split = (int)((nst + want - 1) / want);
     return (nst + *nst_split - 1) / *nst_split;
 }
@@ -385,6 +390,11 @@ extern "C" size_t pcgan_conv2d_hsplit_wgrad_workspace_bytes(const pcgan_conv_des
     return own > other ? own : other;
 }
 
+// host-side record of the last launch of hsplit_wgrad_kernel (pcgan_hwgrad_last_launch): a record of its own, written only when the
+// per-tap kernel itself is launched
+static std::mutex g_hwgrad_mu;
+static int g_hwgrad_rec[PCGAN_HWGRAD_LAUNCH_INFO] = {0};
+
 extern "C" int pcgan_conv2d_bwd_weight_hsplit(const pcgan_conv_desc* d, const void* x, const float* x_amax, int n_xamax, const void* dy,
                                               const float* dy_amax, int n_dyamax, float* dw, int accumulate, void* ws, size_t ws_bytes,
                                               pcgan_stream_t s) {
@@ -408,12 +418,14 @@ extern "C" int pcgan_conv2d_bwd_weight_hsplit(const pcgan_conv_desc* d, const vo
     const void* xin = x;
     const bool inline_reflect = hsplit_wgrad_inline_reflect(d);
     int Hx = Hp, Wx = Wp;
+    int copy = 0;      // which padded-copy kernel ran (the record)
     if (inline_reflect || gen) {
         Hx = d->H;
         Wx = d->W;
     } else if (d->pad > 0) {
         if (int e = launch_pad(x, xpad, d->N * d->C, d->H, d->W, d->pad, d->pad_mode, half, st)) return e;
         xin = xpad;
+        copy = pad_copy_form(d->N * d->C, d->H, d->W, d->pad);
     }
     const int bm = hsplit_wgrad_bm(d), cw = hsplit_wgrad_cw(d);
     HWgradArgs a;
@@ -438,6 +450,20 @@ extern "C" int pcgan_conv2d_bwd_weight_hsplit(const pcgan_conv_desc* d, const vo
         TimerScope timer_main(res_like ? TIMER_RES_WGRAD_MAIN : -1, st);
         e = launch_hsplit_wgrad(a, bm, d->stride, cw, gen, half, grid, st);
     }
+    {
+        std::lock_guard<std::mutex> lk(g_hwgrad_mu);
+        const int v[PCGAN_HWGRAD_LAUNCH_INFO] = {g_hwgrad_rec[0] + 1, bm, d->stride, d->dtype, cw, gen ? 2 : (inline_reflect ? 1 : 0), copy, a.nmt, a.ntile,
+                                                 w.splits, w.nst_split, a.nst};
+        for (int i = 0; i < PCGAN_HWGRAD_LAUNCH_INFO; ++i) g_hwgrad_rec[i] = v[i];
+    }
     if (e) return e;
     return launch_wgrad_reduce(part, dw, w.splits, (size_t)d->K * d->C * d->R * d->S, accumulate, st);
+}
+
+extern "C" int pcgan_hwgrad_last_launch(int* info, int n) {
+    using namespace pcgan;
+    PCGAN_CHECK(info != nullptr && n > 0, "hwgrad_last_launch: null output");
+    std::lock_guard<std::mutex> lk(g_hwgrad_mu);
+    for (int i = 0; i < n; ++i) info[i] = i < PCGAN_HWGRAD_LAUNCH_INFO ? g_hwgrad_rec[i] : 0;
+    return 0;
 }

@@ -124,6 +124,7 @@ static inline size_t es_of(const pcgan_conv_desc* d) { return d->dtype == PCGAN_
 // pieces (np = 2: fp16 pieces scaled per row by rowmax); the data gradient's image(s) of the 3x3 convolution w[K][C][3][3] (nphase = 3:
 // the three row classes, 1: the plain flipped weights); dy -> the weight gradient's A operand; fixed-order sum of the split partials
 int launch_pad(const void* x, void* xpad, int planes, int H, int W, int pad, int reflect, bool half, hipStream_t st);
+int pad_copy_form(int planes, int H, int W, int pad);      // the copy kernel launch_pad picks: 1 = one element per thread, 2 = one wave per plane
 int launch_bsplit_pack(const float* w, void* packed, int M, int C, int T, int nMt, int nst, int bm, int np, const float* rowmax, hipStream_t st);
 int launch_bsplit_pack_dgrad(const float* w, void* packed, int K, int C, int nMt, int nst, int bm, int np, const float* rowmax, int nphase,
                              hipStream_t st);

@@ -146,9 +146,14 @@ __global__ void __launch_bounds__(256) bsplit_pad_wave_kernel(const TA* __restri
     }
 }
 
+int pad_copy_form(int planes, int H, int W, int pad) {
+    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
+    return (Wp % 2 == 0 && Wp <= 128 && Hp * Wp <= 8192 && planes >= 1024) ? 2 : 1;
+}
+
 int launch_pad(const void* x, void* xpad, int planes, int H, int W, int pad, int reflect, bool half, hipStream_t st) {
     const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    if (Wp % 2 == 0 && Wp <= 128 && Hp * Wp <= 8192 && planes >= 1024) {
+    if (pad_copy_form(planes, H, W, pad) == 2) {
         const dim3 grid((planes + 3) / 4);
         if (half) hipLaunchKernelGGL(bsplit_pad_wave_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)x, (bf16*)xpad, planes, H, W, pad, reflect);
         else hipLaunchKernelGGL(bsplit_pad_wave_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (float*)xpad, planes, H, W, pad, reflect);

@@ -1004,6 +1004,18 @@ def wgrad_last_launch():
             'splits': splits, 'units': units}
 
 
+HWGRAD_FIELDS = ('seq', 'bm', 'stride', 'dtype', 'cw', 'form', 'copy', 'row_tiles', 'col_tiles', 'splits', 'stages_per_split', 'stages')
+
+
+def hwgrad_last_launch():
+    """what the last launch of the per-tap weight gradient was (pcgan_hwgrad_last_launch, host memory): HWGRAD_FIELDS -> int; form 0 =
+    separable gather, 1 = reflection in the gather, 2 = zero padding in the gather; copy 0 = none, 1 = element kernel, 2 = wave per
+    plane; seq grows by one per recorded launch"""
+    buf = (ctypes.c_int * len(HWGRAD_FIELDS))()
+    _L.check(_L.load().pcgan_hwgrad_last_launch(buf, len(HWGRAD_FIELDS)), 'hwgrad_last_launch')
+    return dict(zip(HWGRAD_FIELDS, list(buf)))
+
+
 # ---------------------------------------------------------------- pointwise
 def channel_sum(x, accumulate_into=None):
     _chk(accumulate_into)

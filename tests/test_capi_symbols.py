@@ -96,7 +96,7 @@ def test_library_reads_no_environment_and_options_are_explicit():
         assert 'getenv' not in open(src).read(), src
     h = lib.load()
     for key, default in (('bsplit_halo', 1), ('wgrad_gen', 1), ('wgrad_padcopy', 0), ('wgrad_cw', 0), ('hgemm_bf16', 1), ('wgrad_direct', 0),
-                         ('hgemm_tile', 0), ('hgemm_ks', 0), ('wgrad_rowring', 1), ('wgrad_ks', 0)):
+                         ('hgemm_tile', 0), ('hgemm_ks', 0), ('wgrad_rowring', 1), ('wgrad_ks', 0), ('hwgrad_ks', 0)):
         if not any(os.environ.get(e) for e, k, _ in lib._ENV_OPTIONS if k == key):
             assert lib.get_option(key) == default, key
     lib.set_option('wgrad_cw', 256)
@@ -107,6 +107,8 @@ def test_library_reads_no_environment_and_options_are_explicit():
     assert h.pcgan_set_option(b'hgemm_tile', 96096) != 0 and h.pcgan_set_option(b'hgemm_ks', 9) != 0
     assert h.pcgan_set_option(b'wgrad_ks', 513) != 0 and b'wgrad_ks' in h.pcgan_last_error() and h.pcgan_set_option(b'wgrad_ks', -1) != 0
     assert lib.get_option('wgrad_ks') == 0 and not any(k == 'wgrad_ks' for _, k, _ in lib._ENV_OPTIONS)
+    assert h.pcgan_set_option(b'hwgrad_ks', 513) != 0 and b'hwgrad_ks' in h.pcgan_last_error() and h.pcgan_set_option(b'hwgrad_ks', -1) != 0
+    assert lib.get_option('hwgrad_ks') == 0 and not any(k == 'hwgrad_ks' for _, k, _ in lib._ENV_OPTIONS)
 
 
 def test_igemm_launch_record_query():
@@ -135,6 +137,53 @@ def test_wgrad_launch_record_query():
     assert sorted(rec) == ['bm', 'dtype', 'family', 'mode', 'seq', 'splits', 'units', 'variant', 'veca'] and rec['seq'] == buf[0]
     ig2 = (ctypes.c_int * 7)()
     assert h.pcgan_igemm_last_launch(ig2, 7) == 0 and list(ig2) == list(ig)
+
+
+def test_hwgrad_launch_record_query():
+    """pcgan_hwgrad_last_launch reads host memory only (callable without a GPU): entries past the record are 0, a null output and n <= 0
+    are refused, and it is a record of its own -- the query leaves the other two where they were"""
+    import ctypes
+    from pcgan_amd.hip import lib, ops
+    h = lib.load()
+    ig, wg = (ctypes.c_int * 7)(), (ctypes.c_int * 9)()
+    assert h.pcgan_igemm_last_launch(ig, 7) == 0 and h.pcgan_wgrad_last_launch(wg, 9) == 0
+    buf = (ctypes.c_int * 14)(*([-1] * 14))
+    assert h.pcgan_hwgrad_last_launch(buf, 14) == 0 and list(buf)[12:] == [0, 0] and min(buf) >= 0
+    short = (ctypes.c_int * 3)(*([-1] * 3))
+    assert h.pcgan_hwgrad_last_launch(short, 2) == 0 and list(short)[:2] == list(buf)[:2] and short[2] == -1
+    assert h.pcgan_hwgrad_last_launch(None, 12) != 0 and b'hwgrad_last_launch' in h.pcgan_last_error()
+    assert h.pcgan_hwgrad_last_launch(buf, 0) != 0 and h.pcgan_hwgrad_last_launch(buf, -1) != 0
+    rec = ops.hwgrad_last_launch()
+    assert tuple(rec) == ops.HWGRAD_FIELDS and len(rec) == 12 and rec['seq'] == buf[0]
+    ig2, wg2 = (ctypes.c_int * 7)(), (ctypes.c_int * 9)()
+    assert h.pcgan_igemm_last_launch(ig2, 7) == 0 and h.pcgan_wgrad_last_launch(wg2, 9) == 0
+    assert list(ig2) == list(ig) and list(wg2) == list(wg)
+
+
+def test_forced_hwgrad_splits_size_the_workspace():
+    """option "hwgrad_ks" (host arithmetic only): pcgan_conv2d_hsplit_wgrad_workspace_bytes holds exactly the forced number of partial
+    sums, cut to the number of 16-column stages, behind the padded copy where there is one; 0 gives the heuristic's size back"""
+    import ctypes
+    from pcgan_amd.hip import lib
+    h = lib.load()
+
+    def nbytes(d):
+        return int(h.pcgan_conv2d_hsplit_wgrad_workspace_bytes(ctypes.byref(d)))
+
+    def up(v):
+        return (v + 255) // 256 * 256
+    gen = lib.ConvDesc(1, 8, 7, 16, 32, 3, 3, 1, 1, 0, 7, 16)          # zero padding in the gather: 7 stages, no padded copy
+    copy = lib.ConvDesc(1, 8, 7, 16, 32, 5, 5, 1, 2, 0, 7, 16)         # zero padding 2: 7 stages behind a copy of 8 planes of 11 x 20
+    before = [nbytes(d) for d in (gen, copy)]
+    assert before == [32 * 72 * 4, up(8 * 11 * 20 * 4) + 32 * 200 * 4]      # (7 stages: under the 8-stage floor, one split)
+    try:
+        for ks, splits in ((1, 1), (2, 2), (3, 3), (4, 4), (5, 4), (7, 7), (100, 7), (512, 7)):      # (5 over 7: 2 stages per split -> 4)
+            lib.set_option('hwgrad_ks', ks)
+            assert nbytes(gen) == splits * 32 * 72 * 4, ks
+            assert nbytes(copy) == up(8 * 11 * 20 * 4) + splits * 32 * 200 * 4, ks
+    finally:
+        lib.set_option('hwgrad_ks', 0)
+    assert [nbytes(d) for d in (gen, copy)] == before
 
 
 def test_forced_wgrad_splits_size_the_workspace():
