@@ -213,6 +213,14 @@ int pcgan_maxpool_fwd(const void* x, void* y, int32_t* argmax, int NC, int H, in
                       int pad, int P, int Q, int dtype, pcgan_stream_t s);
 int pcgan_maxpool_bwd(const void* dy, const int32_t* argmax, void* dx, int NC, int H, int W, int k, int stride,
                       int pad, int P, int Q, int dtype, pcgan_stream_t s);
+/* AvgPool2d(3, stride=2, padding=[1, 1], count_include_pad=False)  models/networks.py:1897, 1948 (D_NLayersMulti's down-sampler).
+ * count_include_pad=False only: the divisor is the number of taps inside the plane.  fwd: fp32 sum of the in-bounds taps in scan order,
+ * one IEEE division, one rounding.  bwd: a gather, dx = [base +] sum over (p, q) ascending of fp32(dy[p][q] / count(p, q)); base may be
+ * NULL, dx may be base.  P, Q: floor-mode output sizes; pad > k / 2 and non-positive sizes are refused; NC is not limited to 65535. */
+int pcgan_avgpool_fwd(const void* x, void* y, int NC, int H, int W, int k, int stride, int pad, int P, int Q, int dtype,
+                      pcgan_stream_t s);
+int pcgan_avgpool_bwd(const void* dy, const void* base, void* dx, int NC, int H, int W, int k, int stride, int pad, int P, int Q,
+                      int dtype, pcgan_stream_t s);
 int pcgan_global_pool_fwd(const void* x, void* y, int32_t* argmax, int NC, int HW, int is_max, int dtype,
                           pcgan_stream_t s);
 int pcgan_global_pool_bwd(const void* dy, const int32_t* argmax, void* dx, int NC, int HW, int is_max, int dtype,

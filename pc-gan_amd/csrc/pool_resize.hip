@@ -4,6 +4,7 @@
 //
 // Reference: nn.MaxPool2d in models/resnet.py:138 and models/networks.py:1225-1235,
 // nn.AvgPool2d(H)/nn.MaxPool2d(H) in models/networks.py:1056-1059,
+// nn.AvgPool2d(3, stride=2, padding=[1, 1], count_include_pad=False) in models/networks.py:1897, 1948,
 // F.interpolate(mode='bilinear', align_corners=True) in util/util.py:111-117.
 #include "common.h"
 #include <float.h>
@@ -64,6 +65,75 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ dy, const int32_t* __re
             for (int q = q_lo; q <= q_hi; ++q)
                 if (arg[ob + p * Q + q] == me) acc += ld1(dy + ob + p * Q + q);
         st1(dx + i, acc);
+    }
+}
+
+// ---- windowed average pool, count_include_pad=False (the multi-scale discriminator's down-sampler) -------------------------------------
+// taps of the window that starts at `start` and lie inside [0, size)
+__device__ __forceinline__ int avg_taps(int start, int k, int size) {
+    const int lo = start < 0 ? 0 : start;
+    const int hi = start + k > size ? size : start + k;
+    return hi - lo;
+}
+
+// y = (sum of the in-bounds taps, fp32, r outer / s inner) / (their number): one IEEE division, one rounding to the storage type.
+// blockIdx.y strides over the planes (NC may exceed the 65535 of gridDim.y), blockIdx.x over chunks of the output plane.
+template <typename T>
+__global__ void avgpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int NC, int H, int W, int k, int stride, int pad,
+                                   int P, int Q) {
+    for (size_t nc = blockIdx.y; nc < (size_t)NC; nc += gridDim.y) {
+        const T* xp = x + nc * (size_t)H * W;
+        T* yp = y + nc * (size_t)P * Q;
+        for (int me = blockIdx.x * blockDim.x + threadIdx.x; me < P * Q; me += gridDim.x * blockDim.x) {
+            const int p = me / Q;
+            const int q = me - p * Q;
+            const int y0 = p * stride - pad, x0 = q * stride - pad;
+            float acc = 0.f;
+            for (int r = 0; r < k; ++r) {
+                const int iy = y0 + r;
+                if (iy < 0 || iy >= H) continue;
+                for (int s = 0; s < k; ++s) {
+                    const int ix = x0 + s;
+                    if (ix < 0 || ix >= W) continue;
+                    acc += ld1(xp + iy * W + ix);      // (0 + first tap is exact: the sum starts from the first tap)
+                }
+            }
+            st1(yp + me, __fdiv_rn(acc, (float)(avg_taps(y0, k, H) * avg_taps(x0, k, W))));
+        }
+    }
+}
+
+// gather over the input grid: dx = [base +] sum over the outputs (p, q), ascending, whose window holds the element of
+// fp32(dy[p][q] / count(p, q)); the count is recomputed from the indices.  Every thread reads base and writes dx at its own index
+// only, so dx may be base.
+template <typename T>
+__global__ void avgpool_bwd_kernel(const T* __restrict__ dy, const T* base, T* dx, int NC, int H, int W, int k, int stride, int pad,
+                                   int P, int Q) {
+    for (size_t nc = blockIdx.y; nc < (size_t)NC; nc += gridDim.y) {
+        const T* dp = dy + nc * (size_t)P * Q;
+        const size_t ib = nc * (size_t)H * W;
+        for (int me = blockIdx.x * blockDim.x + threadIdx.x; me < H * W; me += gridDim.x * blockDim.x) {
+            const int iy = me / W;
+            const int ix = me - iy * W;
+            // output rows p with p*stride - pad <= iy <= p*stride - pad + k - 1
+            int p_lo = (iy + pad - k + 1 + stride - 1);
+            p_lo = p_lo <= 0 ? 0 : p_lo / stride;
+            int p_hi = (iy + pad) / stride;
+            if (p_hi > P - 1) p_hi = P - 1;
+            int q_lo = (ix + pad - k + 1 + stride - 1);
+            q_lo = q_lo <= 0 ? 0 : q_lo / stride;
+            int q_hi = (ix + pad) / stride;
+            if (q_hi > Q - 1) q_hi = Q - 1;
+            // base is loaded in front of the dy loop, so its latency overlaps theirs (dx may alias it: the load cannot move up on its own)
+            const float b = base != nullptr ? ld1(base + ib + me) : 0.f;
+            float acc = 0.f;
+            for (int p = p_lo; p <= p_hi; ++p) {
+                const int rows = avg_taps(p * stride - pad, k, H);
+                for (int q = q_lo; q <= q_hi; ++q)
+                    acc += __fdiv_rn(ld1(dp + p * Q + q), (float)(rows * avg_taps(q * stride - pad, k, W)));
+            }
+            st1(dx + ib + me, base != nullptr ? acc + b : acc);
+        }
     }
 }
 
@@ -214,6 +284,37 @@ extern "C" int pcgan_maxpool_bwd(const void* dy, const int32_t* argmax, void* dx
     const int bx = (H * W + 255) / 256;
     PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(bx > 1024 ? 1024 : bx, NC), dim3(256), 0, (hipStream_t)s,
                                                     (const T*)dy, argmax, (T*)dx, H, W, k, stride, pad, P, Q, total));
+    PCGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// what the two average-pool entry points check alike; 32 chunks of 256 per plane and sweep (larger planes: grid stride)
+static int avgpool_check(const char* who, int NC, int H, int W, int k, int stride, int pad, int P, int Q) {
+    PCGAN_CHECK(NC > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0 && P > 0 && Q > 0, "%s: sizes must be positive (pad >= 0)", who);
+    PCGAN_CHECK(pad <= k / 2, "%s: pad %d > k / 2 = %d: a window could lie entirely in the padding", who, pad, k / 2);
+    PCGAN_CHECK(((size_t)H + 1) * ((size_t)W + 1) <= 0x7fffffffu && H + 2 * pad >= k && W + 2 * pad >= k, "%s: plane %d x %d out of range for k = %d, pad = %d", who, H, W, k, pad);
+    PCGAN_CHECK(P == (H + 2 * pad - k) / stride + 1 && Q == (W + 2 * pad - k) / stride + 1, "%s: output dims do not match (floor mode)", who);
+    return 0;
+}
+static inline dim3 avgpool_grid(int plane, int NC) { return dim3(capped_blocks((size_t)plane, 256, 32), NC > 65535 ? 65535 : NC); }
+
+extern "C" int pcgan_avgpool_fwd(const void* x, void* y, int NC, int H, int W, int k, int stride, int pad, int P, int Q, int dtype,
+                                 pcgan_stream_t s) {
+    PCGAN_CHECK(x && y, "avgpool_fwd: null x / y");
+    if (avgpool_check("avgpool_fwd", NC, H, W, k, stride, pad, P, Q)) return 1;
+    PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(avgpool_fwd_kernel<T>, avgpool_grid(P * Q, NC), dim3(256), 0, (hipStream_t)s,
+                                                    (const T*)x, (T*)y, NC, H, W, k, stride, pad, P, Q));
+    PCGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pcgan_avgpool_bwd(const void* dy, const void* base, void* dx, int NC, int H, int W, int k, int stride, int pad, int P,
+                                 int Q, int dtype, pcgan_stream_t s) {
+    PCGAN_CHECK(dy && dx, "avgpool_bwd: null dy / dx");
+    PCGAN_CHECK(dy != dx, "avgpool_bwd: dx may alias base, not dy");
+    if (avgpool_check("avgpool_bwd", NC, H, W, k, stride, pad, P, Q)) return 1;
+    PCGAN_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL(avgpool_bwd_kernel<T>, avgpool_grid(H * W, NC), dim3(256), 0, (hipStream_t)s,
+                                                    (const T*)dy, (const T*)base, (T*)dx, NC, H, W, k, stride, pad, P, Q));
     PCGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -593,6 +593,45 @@ def max_pool2d(x, k, stride, pad=0):
     return _MaxPoolFn.apply(x, k, stride, pad)
 
 
+class _AvgPoolPyramidFn(torch.autograd.Function):
+    """(x0, x1, ...): x0 an alias of x, x_{i+1} = avgpool(x_i), one launch per level.  The backward pass folds the gradients from the
+    coarsest level up, g0 + bwd(g1 + bwd(g2 + ...)): one ops.avgpool_bwd launch per level with the level's own gradient riding in as
+    `base`, so autograd adds nothing itself for the image gradient."""
+
+    @staticmethod
+    def forward(ctx, x, levels, k, stride, pad):
+        ctx.set_materialize_grads(False)
+        ctx.cfg = (k, stride, pad)
+        out, cur = [x.view_as(x)], _c(x)
+        for _ in range(levels - 1):
+            cur = ops.avgpool_fwd(cur, k, stride, pad)
+            out.append(cur)
+        ctx.hw = [tuple(t.shape[2:]) for t in out]
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        carry = None
+        for i in range(len(grads) - 1, -1, -1):
+            g = _c(grads[i])
+            carry = g if carry is None else ops.avgpool_bwd(carry, ctx.hw[i], *ctx.cfg, base=g)
+        return carry, None, None, None, None
+
+
+def avg_pool_pyramid(x, levels, k=3, stride=2, pad=1):
+    """The image pyramid of the multi-scale discriminator (reference models/networks.py:1897, 1940-1949): (x0, ..., x_{levels-1}) with
+    x0 = x (an alias) and x_{i+1} = AvgPool2d(k, stride, pad, count_include_pad=False)(x_i).  Levels whose gradient is None are skipped
+    in the backward pass; levels == 1 returns (x,) without a launch."""
+    if levels < 1:
+        raise ValueError('pcgan_amd: avg_pool_pyramid needs levels >= 1, got %r' % (levels,))
+    if levels == 1:
+        ops._act(_c(x))      # refuses CPU tensors and foreign dtypes although nothing is launched
+        return (x,)
+    return _AvgPoolPyramidFn.apply(x, levels, k, stride, pad)
+
+
 class _GlobalPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, is_max):

@@ -100,6 +100,8 @@ SIGNATURES = {
     'pcgan_sum_planes': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'pcgan_maxpool_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pcgan_maxpool_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pcgan_avgpool_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pcgan_avgpool_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pcgan_global_pool_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'pcgan_global_pool_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'pcgan_bilinear_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

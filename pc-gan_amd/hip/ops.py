@@ -1449,6 +1449,31 @@ def maxpool_bwd(dy, arg, in_hw, k, stride, pad):
     return dx
 
 
+def avgpool_fwd(x, k, stride, pad):
+    """nn.AvgPool2d(k, stride, pad, count_include_pad=False), floor mode"""
+    dt = _act(x)
+    N, C, H, W = x.shape
+    P, Q = conv_out_size(H, k, stride, pad), conv_out_size(W, k, stride, pad)
+    y = torch.empty((N, C, P, Q), dtype=x.dtype, device=x.device)
+    _L.check(_L.load().pcgan_avgpool_fwd(_p(x), _p(y), N * C, H, W, k, stride, pad, P, Q, dt, _stream()), 'avgpool_fwd')
+    return y
+
+
+def avgpool_bwd(dy, hw, k, stride, pad, base=None, out=None):
+    """The gradient of avgpool_fwd at an (N, C, *hw) input, plus `base` when given (one launch, one rounding).  The result is a fresh
+    tensor, or `out` -- which may be `base` itself, and nothing else that overlaps an operand."""
+    dt = _act(dy, base, out)
+    N, C, P, Q = dy.shape
+    H, W = hw
+    shape = (N, C, H, W)
+    for name, t in (('base', base), ('out', out)):
+        if t is not None and tuple(t.shape) != shape:
+            raise RuntimeError('pcgan_amd: avgpool_bwd %s of shape %s for a gradient of shape %s' % (name, tuple(t.shape), shape))
+    dx = out if out is not None else torch.empty(shape, dtype=dy.dtype, device=dy.device)
+    _L.check(_L.load().pcgan_avgpool_bwd(_p(dy), _p(base), _p(dx), N * C, H, W, k, stride, pad, P, Q, dt, _stream()), 'avgpool_bwd')
+    return dx
+
+
 def global_pool_fwd(x, is_max):
     dt = _act(x)
     N, C, H, W = x.shape

@@ -144,8 +144,14 @@ def define_D(input_nc, nz, ndf, which_model_netD, n_layers_D=3, norm='batch', us
     elif which_model_netD == 'n_layers_proj':
         netD = NLayerProjectionDiscriminator(input_nc, nz, ndf, n_layers_D, norm_layer=norm_layer, use_sigmoid=use_sigmoid,
                                              proj=use_projection)
-    elif which_model_netD in ('n_layers_multi', 'pixel', 'pyramid', 'gan_stability',
-                              'gan_stability_class', 'mnist_fc'):
+    elif which_model_netD == 'n_layers_multi':
+        if nz >= 1:
+            raise NotImplementedError('Discriminator [n_layers_multi] with a rating (nz = %d) is outside the MI355X hot path (SURVEY.md '
+                                      'section 8): the reference\'s multi-scale discriminator is unconditional -- it drops nz and its '
+                                      'forward takes the image alone; use it with --model wsgan_cycle, or basic / n_layers here' % nz)
+        netD = D_NLayersMulti(input_nc, ndf, n_layers=n_layers_D, norm_layer=norm_layer, use_sigmoid=use_sigmoid, gpu_ids=gpu_ids,
+                              num_D=num_Ds)
+    elif which_model_netD in ('pixel', 'pyramid', 'gan_stability', 'gan_stability_class', 'mnist_fc'):
         raise NotImplementedError('Discriminator [%s] is outside the MI355X hot path (SURVEY.md section 8); '
                                   'use basic / n_layers' % which_model_netD)
     else:
@@ -502,6 +508,66 @@ class NLayerProjectionDiscriminator(tnn.Module):
         if y.numel() not in (self.nz, p.shape[0] * self.nz):
             raise RuntimeError('pcgan_amd: y of shape %s for batch %d and nz = %d' % (tuple(y.shape), p.shape[0], self.nz))
         return HF.projection_head(p, y.reshape(-1, self.nz), self.psi.weight, self.psi.bias, self.l_y.weight, self.l_y.bias, self._sigm)
+
+
+class D_NLayersMulti(tnn.Module):
+    """reference models/networks.py:1883-1949: the multi-scale PatchGAN.  Unconditional: forward(input) only.  num_D == 1 is one
+    Sequential `model` and returns a tensor; num_D > 1 registers `model0`, `model1`, ... on the module itself (the reference's
+    ListModule), scale i + 1 judging AvgPool2d(3, stride=2, padding=1, count_include_pad=False) of scale i's image, and returns the
+    list of patch maps that GANLoss sums over.  Unlike NLayerDiscriminator EVERY convolution carries a bias, also in front of a batch
+    norm, and the widths shrink cumulatively: ndf = int(round(ndf / 2 ** (i + 1))) on the running ndf (64, 32, 8; 16, 8, 2; 8, 4, 1).
+    Modules are created in the reference's order, so a seeded construction draws the same initial weights."""
+
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=hnn.BatchNorm2d, use_sigmoid=False, gpu_ids=[], num_D=1):
+        super().__init__()
+        if num_D < 1 or n_layers < 1:
+            raise ValueError('pcgan_amd: D_NLayersMulti needs num_D >= 1 and n_layers >= 1, got %r and %r' % (num_D, n_layers))
+        self.gpu_ids, self.num_D, self.n_layers = gpu_ids, num_D, n_layers
+        if num_D == 1:
+            self.model = tnn.Sequential(*self.get_layers(input_nc, ndf, n_layers, norm_layer, use_sigmoid))
+            return
+        self.add_module('model0', tnn.Sequential(*self.get_layers(input_nc, ndf, n_layers, norm_layer, use_sigmoid)))
+        for i in range(num_D - 1):
+            ndf = int(round(ndf / (2 ** (i + 1))))
+            if ndf < 1:     # (the reference builds convolutions without channels here and dies in its first forward)
+                raise ValueError('pcgan_amd: D_NLayersMulti scale %d of %d has no channels left; raise --ndf or lower --num_Ds' % (i + 1, num_D))
+            self.add_module('model%d' % (i + 1), tnn.Sequential(*self.get_layers(input_nc, ndf, n_layers, norm_layer, use_sigmoid)))
+
+    @staticmethod
+    def get_layers(input_nc, ndf=64, n_layers=3, norm_layer=hnn.BatchNorm2d, use_sigmoid=False):
+        seq = [hnn.Conv2d(input_nc, ndf, kernel_size=4, stride=2, padding=1), tnn.LeakyReLU(0.2, True)]
+        mult = 1
+        for n in range(1, n_layers):
+            prev, mult = mult, min(2 ** n, 8)
+            seq += [hnn.Conv2d(ndf * prev, ndf * mult, kernel_size=4, stride=2, padding=1), norm_layer(ndf * mult),
+                    tnn.LeakyReLU(0.2, True)]
+        prev, mult = mult, min(2 ** n_layers, 8)
+        seq += [hnn.Conv2d(ndf * prev, ndf * mult, kernel_size=4, stride=1, padding=1), norm_layer(ndf * mult), tnn.LeakyReLU(0.2, True)]
+        seq += [hnn.Conv2d(ndf * mult, 1, kernel_size=4, stride=1, padding=1)]
+        if use_sigmoid:
+            seq += [tnn.Sigmoid()]
+        return seq
+
+    def min_side(self):
+        """The smallest input side every scale's stack accepts.  A stack halves n_layers times (floor) and then loses one pixel in each
+        of its two stride-1 4x4 convolutions, so it needs 3 * 2**n_layers; the pool maps a side s to ceil(s / 2), so each further scale
+        asks for 2 * m - 1 in front of it."""
+        m = 3 * 2 ** self.n_layers
+        for _ in range(self.num_D - 1):
+            m = 2 * m - 1
+        return m
+
+    def forward(self, input):
+        side = min(input.shape[2], input.shape[3])
+        if side < self.min_side():
+            raise ValueError('pcgan_amd: D_NLayersMulti input %d x %d is too small: with n_layers = %d and num_D = %d the coarsest scale '
+                             'needs an input side of at least %d' % (input.shape[2], input.shape[3], self.n_layers, self.num_D, self.min_side()))
+        if self.num_D == 1:
+            return run_sequential(self.model, input)
+        # the image arrives in the model's activation storage type (BaseModel.to_act / the generator's output): the pyramid keeps it,
+        # so under --dtype bf16 there is one cast in front of the pyramid and none per scale
+        scales = HF.avg_pool_pyramid(input, self.num_D)
+        return [run_sequential(getattr(self, 'model%d' % i), x) for i, x in enumerate(scales)]
 
 
 # ------------------------------------------------------------------------- encoders
