@@ -11,8 +11,8 @@ case claims against it without a GPU; the GPU test holds `want` against what the
 Data: |x|, |w|, |dy|, |bias| uniform in [0.75, 1.25] with independent random signs, so every term of every sum has a magnitude in
 [0.5625, 1.5625]; bf16 cases round the activation tensor to bf16 first and the reference sees the stored values (the weights stay fp32:
 these kernels take them as fp32).
-Reference: oracle.ops_ref.conv2d in float64, its autograd for the data gradient (reflection padding included); the same call on absolute
-values gives A, the per-element sum of |terms|.
+Reference: split_arith.reference -- oracle.ops_ref.conv2d in float64, its autograd for the data gradient (reflection padding included); the
+same call on absolute values gives A, the per-element sum of |terms|.
 
 Bound, fp32 storage, per element:  |y - ref| <= 2 n_eff 2^-24 A,  n_eff = Kp of the element's phase + K slices + 8: the standard bound
 of an fp32 sum of that many terms in any order, with a factor 2 for the product rounded before it is added (the fp32 MFMA and the fused
@@ -48,10 +48,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ops_ref as R
+from split_arith import U, SLOPE, cdiv, out_size, reference
 
-U = 2.0 ** -24
 TERM_MIN = 0.75 * 0.75      # the smallest possible |term|; the largest is 1.25 * 1.25
-SLOPE = 0.2
 NTAP_FWD, NTAP_MIR, NTAP_CG4 = 25, 9, 49
 ACT_NAMES = ('none', 'relu', 'lrelu', 'tanh', 'sigmoid')
 
@@ -60,16 +59,8 @@ Plan = collections.namedtuple('Plan', 'form mode bm bp ks nphase M Cg Cgp phases
 Phase = collections.namedtuple('Phase', 'fy fx nR nS Hs Ws Kp Ptot')
 
 
-def cdiv(a, b):
-    return -(-a // b)
-
-
 def round4(v):
     return (v + 3) & ~3
-
-
-def out_size(H, k, stride, pad):
-    return (H + 2 * pad - k) // stride + 1
 
 
 # ---- the host's routing, restated ------------------------------------------------------------------------------------------------------------
@@ -262,18 +253,6 @@ def _signed(g, *shape):
     return mag * (torch.randint(0, 2, shape, generator=g) * 2 - 1).float()
 
 
-def _fwd64(src, w, b, geom):
-    return R.conv2d(src, w, b, geom[7], geom[8], geom[9])
-
-
-def _dgrad64(dy, w, b, geom):
-    N, C, H, W = geom[:4]
-    xz = torch.zeros(N, C, H, W, dtype=torch.float64, requires_grad=True)
-    R.conv2d(xz, w, None, geom[7], geom[8], geom[9]).backward(dy)
-    g = xz.grad.detach()
-    return g if b is None else g + b.view(1, -1, 1, 1)
-
-
 def _fold_images(dy, w, geom):
     """T = sum over the mirror images of |gradient of the reflection-padded tensor| (the padded fallback stores each image before the fold)"""
     N, C, H, W, K, Rr, S, st, pad, pm = geom
@@ -300,13 +279,10 @@ def _data(pass_, geom, half, bias, seed):
         src = src.bfloat16()
     for t in (src.float(), w) + ((b,) if bias else ()):
         assert 0.75 <= float(t.abs().min()) and float(t.abs().max()) <= 1.25
-    s64, w64, b64 = src.double(), w.double(), (b.double() if bias else None)
-    f = _fwd64 if pass_ == 'fwd' else _dgrad64
-    ref = f(s64, w64, b64, geom)
-    A = f(s64.abs(), w64.abs(), b64.abs() if bias else None, geom)
+    ref, A = reference(pass_, geom, src, w, b)
     T = None
     if pass_ == 'dgrad' and pm == 1:
-        T = _fold_images(s64, w64, geom)
+        T = _fold_images(src.double(), w.double(), geom)
     return Data(src, w, b, ref, A, T)
 
 

@@ -9,7 +9,7 @@ bsplit_halo is 1) x image width in (32, 64).  A case is one direct call of the C
 channels): the data gradient gathers the K channels of the convolution and produces its C.  `accepts` restates halo_geometry.
 
 Section A, kind 'signed' (conv_f32_cases._signed): |x|, |w|, |dy|, |bias|, |addend| in [0.75, 1.25] with random signs; tanh / sigmoid cases
-multiply the weights by 2^wexp so that |ref| stays near 1.  Reference: conv_f32_cases._fwd64 / _dgrad64 (float64, autograd through the
+multiply the weights by 2^wexp so that |ref| stays near 1.  Reference: split_arith.reference (float64, autograd through the
 reflection); the same call on absolute values gives A.  Kp = 9 x gathered channels terms per element.  Per element |y - ref| <= E:
   f16x2   E = (2 (3 Kp + 8) 2^-24 + 2^-20) A.  Each scaled operand splits as h + l with relative error <= 2^-22, the dropped (l,l) product
           is <= 2^-22 of the term, with the second-order terms under 2^-20.  The three piece products per term are exact in fp32 and
@@ -52,15 +52,15 @@ one low piece is zeroed, one window entry takes a wrong source, or one tap is sh
 Section C data: `range_data` (randn under the kinds of tests/test_gpu_bf16x6.py), the maxima-slot case, the four-corner overflow data."""
 import collections
 import functools
-import math
 
 import torch
 
 from oracle import ops_ref as R
-from conv_f32_cases import _signed, _fwd64, _dgrad64, TERM_MIN, SLOPE
+import split_arith
+from conv_f32_cases import _signed, TERM_MIN
+# (SLOPE, per_row_rel: the tests reach them through this module)
+from split_arith import U, SLOPE, _ints, _bf16, _fwd64, _dgrad64, half_ulp_bf16, pow2_scale, split2h, split3, per_row_rel, range_scale
 
-U = 2.0 ** -24
-SLOPE_EXACT = 0.25
 NT = 512                        # threads of a workgroup (thread_max_of_partials strides by it)
 PKS = ('f16x2', 'bf16x3', 'bf16')
 INSTANTIATIONS = tuple((p, k, w) for p in ('fwd', 'dgrad') for k in PKS for w in (32, 64))
@@ -143,14 +143,6 @@ def fold_mask(fold, H, W):
 
 
 # ---- data, reference, bound ------------------------------------------------------------------------------------------------------------------
-def _ints(g, lo, hi, shape):
-    return torch.randint(lo, hi + 1, shape, generator=g).float()
-
-
-def _bf16(t):
-    return t.bfloat16().float()
-
-
 @functools.lru_cache(maxsize=None)
 def data(c):
     """(src, w, bias, addend, float64 reference BEFORE the activation and the addend, A, row exponents) of a case on the CPU: made once,
@@ -213,19 +205,11 @@ def data(c):
 
 def reference(c, src, w, b):
     """(float64 result before the activation, the same call on absolute values) of the case's geometry on the given operands"""
-    f = _fwd64 if c.pass_ == 'fwd' else _dgrad64
-    s64, w64, b64 = src.double(), w.double(), (b.double() if b is not None else None)
-    return f(s64, w64, b64, geom(c)), f(s64.abs(), w64.abs(), b64.abs() if b is not None else None, geom(c))
+    return split_arith.reference(c.pass_, geom(c), src, w, b)
 
 
 def slope_of(c):
-    return SLOPE if c.kind == 'signed' else SLOPE_EXACT
-
-
-def half_ulp_bf16(v):
-    """half the spacing of bf16 numbers (8 significant bits) at magnitude v"""
-    e = torch.frexp(v.abs().clamp_min(2.0 ** -120))[1]
-    return torch.pow(2.0, (e - 9).double())
+    return split_arith.slope_of(c.kind)
 
 
 def expected(c, ref=None):
@@ -260,38 +244,10 @@ def condition(c):
 
 def quanta(c):
     """exact kinds: the largest A of the case in units of its quantum (1, or 2^j of the row for 'wlow' on f16x2); must stay under 2^24"""
-    d = data(c)
-    if d.rowexp is None:
-        return float(d.A.max())
-    return float((d.A / torch.pow(2.0, d.rowexp.double()).view(1, -1, 1, 1)).max())
+    return split_arith.quanta(data(c))
 
 
 # ---- the kernel's arithmetic in torch --------------------------------------------------------------------------------------------------------
-def pow2_scale(amax):
-    """common.h: the power of two that puts amax into [2^13, 2^14); 1 for 0; exponent clamped to +-100"""
-    if not amax > 0.0:
-        return 1.0
-    e = 14 - math.frexp(amax)[1]
-    return 2.0 ** max(-100, min(100, e))
-
-
-def split2h(x, sums=False):
-    """fp32 tensor -> (h, l) fp16 pieces as fp32 tensors; the split must not overflow fp16.  sums: the window of the data gradient, whose
-    sum entries reach up to 4 (2^14 - 1): below 2^16 the high piece saturates at 65504 and the low piece takes the rest"""
-    xs = torch.where(x.abs() < 65536.0, x.clamp(-65504.0, 65504.0), x) if sums else x
-    h = xs.half()
-    l = (x - h.float()).half()
-    assert bool(torch.isfinite(h).all()), 'a scaled operand overflows fp16'
-    return [h.float(), l.float()]
-
-
-def split3(x):
-    h = x.bfloat16().float()
-    r1 = x - h
-    m = r1.bfloat16().float()
-    return [h, m, (r1 - m).bfloat16().float()]
-
-
 def window(c, src, wrong=None):
     """what the nine taps of every output pixel read, [N][G][H][W][3][3] in fp32.  forward: the reflection-padded input.  data gradient:
     dy with a ring of zeros, except that row 1 reads the sum dy[2] + dy[0] through tap 2 and row H-2 the sum dy[H-3] + dy[H-1] through
@@ -358,7 +314,7 @@ def emulate(c, perturb=None):
     if c.pk == 'f16x2':
         sx = pow2_scale(float(d.src.abs().max()))
         sw = torch.tensor([pow2_scale(float(v)) for v in wm.abs().amax(dim=(1, 2, 3))])
-        xp, wp = split2h(win * sx, dg), split2h(wm * sw.view(M, 1, 1, 1))
+        xp, wp = list(split2h(win * sx, sums=dg)), list(split2h(wm * sw.view(M, 1, 1, 1)))
         pairs = ((1, 0), (0, 1), (0, 0))                   # (weight piece, window piece): (l,h) (h,l) (h,h)
     elif c.pk == 'bf16x3':
         xp, wp = split3(win), split3(wm)
@@ -419,35 +375,19 @@ def range_data(c, kind):
     g = torch.Generator().manual_seed(2000 + RANGE_KINDS.index(kind) + (17 if c.pass_ == 'fwd' else 0) + W)
     src = torch.randn(N, G, H, W, generator=g)
     w = torch.randn(gm[4], gm[1], 3, 3, generator=g) * 0.05
-    if kind == 'wide_range':        # magnitudes over twelve decades inside one tensor
-        src = src * torch.pow(10.0, torch.rand(src.shape, generator=g) * 12 - 9)
-        w = w * torch.pow(10.0, torch.rand(w.shape, generator=g) * 6 - 3)
-    elif kind == 'tiny':
-        src, w = src * 1e-30, w * 1e-6
-    else:
-        src, w = src * 1e12, w * 1e8
+    # wide_range: magnitudes over twelve decades inside one tensor
+    src, w = range_scale(kind, g, src, w, (12, -9), (6, -3), (1e-30, 1e-6), (1e12, 1e8))
     f = _fwd64 if c.pass_ == 'fwd' else _dgrad64
     return src, w, f(src.double(), w.double(), None, gm)
-
-
-def per_row_rel(out, ref):
-    """relative L2 error of every produced channel"""
-    rows = ref.shape[1]
-    dd = (out - ref).transpose(0, 1).reshape(rows, -1).norm(dim=1)
-    return dd / ref.transpose(0, 1).reshape(rows, -1).norm(dim=1)
 
 
 MAXPOS_N = (1, 2, 3, 4, 5, 7, 2047, 2048, 2049, 8192, 8200, 8203)
 
 
 def maxima_slots(n):
-    """where the true maximum is put in a maxima array of n slots: first, last, and from 4 NT = 2048 slots on the last lane of the float4 at
-    index 4 NT - 1 (the end of the first 4-in-flight round of NT threads; the float4 remainder when n / 4 is under 4 NT + 1) and the last
-    element the float4 loops read"""
-    pos = [0, n - 1]
-    if n >= 4 * NT:
-        pos += [p for p in (4 * (4 * NT - 1) + 3, 4 * (n // 4) - 1) if p < n]
-    return sorted(set(pos))
+    """split_arith.maxima_slots at NT = 512: from 4 NT = 2048 slots on the end of the first 4-in-flight round, from 16 NT = 8192 on the
+    second and the third load in flight"""
+    return split_arith.maxima_slots(n, NT)
 
 
 def corner_data(c, which):

@@ -13,7 +13,7 @@ no fused reflect gradient and BM >= 64), and `claims` are the predicates of the 
 CLAIMS below).  `supported` restates pcgan_conv2d_hgemm_supported.
 
 Section A, kind 'signed' (conv_f32_cases._signed): |x|, |w|, |dy|, |bias| in [0.75, 1.25] with random signs; tanh / sigmoid cases multiply
-the weights by 2^wexp so that |ref| stays near 1.  Reference: conv_f32_cases._fwd64 / _dgrad64 in float64; the same call on absolute
+the weights by 2^wexp so that |ref| stays near 1.  Reference: split_arith.reference in float64; the same call on absolute
 values gives A.  Per element, Kp = the K length of the phase that owns it, ks = the K slices of the launch:
   fp32 tensors  |y - act(ref)| <= (2 (3 Kp + ks + 8) 2^-24 + 2^-20) A (+ 2^-22 |act(ref)|).  Each scaled operand splits as h + l with
                 relative error <= 2^-22, the dropped (l,l) product is <= 2^-22 of the term, second-order terms under 2^-20 (the
@@ -37,23 +37,21 @@ fp32 accumulation is exact when A < 2^24 quanta (asserted per case; at 15 bits K
   bf16 tensors: 8-bit integers in both operands; the expected value is the exact integer rounded to bf16 to nearest even.
   'xlow16' (section C): 'xlow' with every magnitude but the pinned one <= 16: the maxima array is built by hand around it.
 
-`emulate` restates the kernel's arithmetic in torch: the scale of x from the maxima, split2h, the pre-split weights per row, the three
+`emulate` restates the kernel's arithmetic in torch: the scale of x from the maxima, split_arith.split2h, the pre-split weights per row, the three
 piece products in the kernel's order (l,h) (h,l) (h,h) accumulated in fp32 stage by stage in the kernel's K order (16-channel chunk, tap,
 channel), slice by slice, the slice sum, (acc isx) isw, bias, activation.  A fault made on purpose is not run on a GPU: the sensitivity
 study applies PERTURBATIONS to `emulate` and evaluates the gates of both sections on its result (tests/test_hgemm_cases.py)."""
 import collections
 import functools
-import math
 
 import torch
 
 from oracle import ops_ref as R
 import conv_f32_cases as F
-from conv_f32_cases import plan, record, _signed, _fwd64, _dgrad64, out_size, TERM_MIN
+import split_arith
+from conv_f32_cases import plan, record, _signed, TERM_MIN      # (record, SLOPE, per_row_rel: the tests reach them through this module)
+from split_arith import U, SLOPE, cdiv, out_size, _ints, _bf16, _fwd64, _dgrad64, pow2_scale, split2h, per_row_rel, range_scale
 
-U = 2.0 ** -24
-SLOPE = 0.2
-SLOPE_EXACT = 0.25
 NT = 256                        # threads of a workgroup (thread_max_of_partials strides by it)
 ACT_NAMES = ('none', 'relu', 'lrelu', 'tanh', 'sigmoid')
 KINDS = ('signed', 'xlow', 'wlow', 'xlow16')
@@ -64,10 +62,6 @@ FORMS = {False: 'hgemm_f16x2', True: 'hgemm_bf16'}
 
 Case = collections.namedtuple('Case', 'sect name pass_ geom tile ks half act bias wexp kind want claims seed')
 Data = collections.namedtuple('Data', 'src w b ref A rowexp')
-
-
-def cdiv(a, b):
-    return -(-a // b)
 
 
 # ---- the host, restated ----------------------------------------------------------------------------------------------------------------------
@@ -145,14 +139,6 @@ def holds(case, claim):
 
 
 # ---- data, reference, bound ------------------------------------------------------------------------------------------------------------------
-def _ints(g, lo, hi, shape):
-    return torch.randint(lo, hi + 1, shape, generator=g).float()
-
-
-def _bf16(t):
-    return t.bfloat16().float()
-
-
 def shapes(case):
     """(shape of the gathered tensor, shape of the produced tensor, rows of the pass's weight matrix)"""
     N, C, H, W, K, Rr, S, st, pad, pm = case.geom
@@ -163,9 +149,7 @@ def shapes(case):
 
 
 def reference(case, src, w, b):
-    f = _fwd64 if case.pass_ == 'fwd' else _dgrad64
-    s64, w64, b64 = src.double(), w.double(), (b.double() if b is not None else None)
-    return f(s64, w64, b64, case.geom), f(s64.abs(), w64.abs(), b64.abs() if b is not None else None, case.geom)
+    return split_arith.reference(case.pass_, case.geom, src, w, b)
 
 
 @functools.lru_cache(maxsize=None)
@@ -211,7 +195,7 @@ def data(case):
 
 
 def slope_of(case):
-    return SLOPE if case.kind == 'signed' else SLOPE_EXACT
+    return split_arith.slope_of(case.kind)
 
 
 def expected(case, ref=None):
@@ -251,10 +235,7 @@ def condition(case):
 
 def quanta(case):
     """exact kinds: the largest A of the case in units of its quantum (1, or 2^j of the row for 'wlow' on fp32 tensors)"""
-    d = data(case)
-    if d.rowexp is None:
-        return float(d.A.max())
-    return float((d.A / torch.pow(2.0, d.rowexp.double()).view(1, -1, 1, 1)).max())
+    return split_arith.quanta(data(case))
 
 
 def exact_expected(case):
@@ -267,22 +248,6 @@ def exact_expected(case):
 
 
 # ---- the kernel's arithmetic in torch --------------------------------------------------------------------------------------------------------
-def pow2_scale(amax):
-    """common.h: the power of two that puts amax into [2^13, 2^14); 1 for 0; exponent clamped to +-100"""
-    if not amax > 0.0:
-        return 1.0
-    e = 14 - math.frexp(amax)[1]
-    return 2.0 ** max(-100, min(100, e))
-
-
-def split2h(x):
-    """fp32 tensor -> (h, l) fp16 pieces as fp32 tensors"""
-    h = x.half()
-    l = (x - h.float()).half()
-    assert bool(torch.isfinite(h).all()), 'a scaled operand overflows fp16'
-    return h.float(), l.float()
-
-
 def row_maxima(case, w):
     return w.abs().amax(dim=(1, 2, 3)) if case.pass_ == 'fwd' else w.abs().amax(dim=(0, 2, 3))
 
@@ -470,38 +435,19 @@ def range_data(case, kind):
     g = torch.Generator().manual_seed(3000 + RANGE_KINDS.index(kind) + (17 if case.pass_ == 'fwd' else 0) + case.tile)
     src = torch.randn(*sshape, generator=g)
     w = torch.randn(K, C, Rr, S, generator=g) * 0.05
-    if kind == 'wide_range':        # magnitudes over twelve decades inside one tensor
-        src = src * torch.pow(10.0, torch.rand(src.shape, generator=g) * 12 - 9)
-        w = w * torch.pow(10.0, torch.rand(w.shape, generator=g) * 6 - 3)
-    elif kind == 'tiny':
-        src, w = src * 1e-30, w * 1e-6
-    else:
-        src, w = src * 1e12, w * 1e8
+    # wide_range: magnitudes over twelve decades inside one tensor
+    src, w = range_scale(kind, g, src, w, (12, -9), (6, -3), (1e-30, 1e-6), (1e12, 1e8))
     f = _fwd64 if case.pass_ == 'fwd' else _dgrad64
     return src, w, f(src.double(), w.double(), None, case.geom)
-
-
-def per_row_rel(out, ref):
-    """relative L2 error of every produced channel"""
-    rows = ref.shape[1]
-    dd = (out - ref).transpose(0, 1).reshape(rows, -1).norm(dim=1)
-    return dd / ref.transpose(0, 1).reshape(rows, -1).norm(dim=1)
 
 
 MAXPOS_N = (1, 2, 3, 4, 5, 7, 1023, 1024, 1025, 4096, 4104, 4107)
 
 
 def maxima_slots(n):
-    """where the true maximum is put in a maxima array of n slots (halo_cases.maxima_slots at NT = 256): first, last, and from 4 NT = 1024
-    slots on the last lane of the float4 at index 4 NT - 1 (the end of the first 4-in-flight round of NT threads; the float4 remainder
-    when n / 4 is under 4 NT + 1) and the last element the float4 loops read; from 16 NT slots on also in the second and the third of
-    the four loads in flight, which the first and the last slot of a round do not reach"""
-    pos = [0, n - 1]
-    if n >= 4 * NT:
-        pos += [q for q in (4 * (4 * NT - 1) + 3, 4 * (n // 4) - 1) if q < n]
-    if n >= 16 * NT:      # the 4-in-flight loop runs: one slot in its second and one in its third load (p4[i + NT], p4[i + 2 NT])
-        pos += [4 * NT + 1, 4 * (2 * NT + 77) + 2]
-    return sorted(set(pos))
+    """split_arith.maxima_slots at NT = 256: from 4 NT = 1024 slots on the end of the first 4-in-flight round, from 16 NT = 4096 on the
+    second and the third load in flight"""
+    return split_arith.maxima_slots(n, NT)
 
 
 # ---- the table -------------------------------------------------------------------------------------------------------------------------------

@@ -50,7 +50,7 @@ With 15-bit random values a mirrored, shifted or un-zeroed source element cannot
 table appears in this section too.
 
 `emulate` restates the kernel's arithmetic in torch: which source element (or zero) every (stage, pixel, column) of the gather ends up
-with and which dy values the `am` mask of a ragged row lets in, the scales from the maxima (pow2_scale), split2h of both operands, the three piece
+with and which dy values the `am` mask of a ragged row lets in, the scales from the maxima (split_arith.pow2_scale), split_arith.split2h of both operands, the three piece
 products in the kernel's order (dy_l x_h) (dy_h x_l) (dy_h x_h) accumulated in fp32 stage by stage, split by split, (acc isx) isd, the
 two-accumulator reduce of bsplit_wgrad_reduce_kernel.  A fault made on purpose is never run on a GPU: PERTURBATIONS are applied to
 `emulate`, and tests/test_hsplit_wgrad_cases.py evaluates the gates of both sections on the result.
@@ -60,14 +60,13 @@ and the border perturbations are faults of that index (what the element would ho
 sensitivity study; the GPU gates do not lean on it, their reference is float64 autograd."""
 import collections
 import functools
-import math
 
 import torch
 
 from oracle import ops_ref as R
 from conv_f32_cases import _signed
+from split_arith import U, cdiv, out_size, pow2_scale, split2h
 
-U = 2.0 ** -24
 TERM_MIN = 0.75 * 0.75
 F32, BF16 = 0, 1
 OPTIONS = {'wgrad_gen': 1, 'wgrad_padcopy': 0, 'wgrad_cw': 0, 'wgrad_rowring': 1, 'hwgrad_ks': 0}      # the library's defaults
@@ -91,14 +90,6 @@ UNREACHABLE = ((256, 2, F32, 2, 0),)
 Case = collections.namedtuple('Case', 'sect name geom half opts kind maxima want claims')
 Data = collections.namedtuple('Data', 'x dy ref A')
 Plan = collections.namedtuple('Plan', RECORD + ('ws_bytes', 'P', 'Q', 'Qs', 'nwg', 'here'))
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def out_size(H, k, stride, pad):
-    return (H + 2 * pad - k) // stride + 1
 
 
 def options(opts):
@@ -505,22 +496,6 @@ def gate(case, out, d, splits, stages_per_split):
 
 
 # ---- the kernel's arithmetic, restated -------------------------------------------------------------------------------------------------------
-def pow2_scale(amax):
-    """common.h: the power of two that puts amax into [2^13, 2^14); 1 for 0; exponent clamped to +-100"""
-    if not amax > 0.0:
-        return 1.0
-    e = 14 - math.frexp(amax)[1]
-    return 2.0 ** max(-100, min(100, e))
-
-
-def split2h(x, may_overflow=False):
-    """fp32 tensor -> (h, l) fp16 pieces as fp32 tensors"""
-    h = x.half()
-    l = (x - h.float()).half()
-    assert may_overflow or bool(torch.isfinite(h).all()), 'a scaled operand overflows fp16'
-    return h.float(), l.float()
-
-
 PERTURBATIONS = (
     'left_not_zeroed',        # GEN: the element in front of column 0 is read as memory holds it (the element before, 0 in front of the tensor)
     'rotate_without_zero',    # GEN: the run loaded one element late is rotated but its element 0 keeps the first loaded value (column -1 + stride)
@@ -633,7 +608,7 @@ def emulate(case, perturb=None):
             mx, md = (mx * DECOY, md) if perturb[0] == 'x' else (mx, md * DECOY)
         sx, sdy = pow2_scale(mx), pow2_scale(md)
         missed = perturb in ('x_maximum_slot_missed', 'dy_maximum_slot_missed')
-        (dh, dl), (xh, xl) = split2h(dyg * sdy, missed), split2h(xg * sx, missed)
+        (dh, dl), (xh, xl) = split2h(dyg * sdy, may_overflow=missed), split2h(xg * sx, may_overflow=missed)
         prods = [(dl, xh), (dh, xl), (dh, xh)]
         if perturb == 'drop_lh':
             del prods[0]

@@ -72,6 +72,7 @@ import pytest
 import torch
 
 import conv_f32_cases as T
+from gpu_direct import VP, ptr, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -113,19 +114,15 @@ def _direct(dev, c, src, w, b):
     d = ops.make_desc(*c.geom, ops.BF16 if c.half else ops.F32)
     fwd = c.pass_ == 'fwd'
     nb = int(lib.pcgan_conv2d_workspace_bytes(ctypes.byref(d), L.PASS_FWD if fwd else L.PASS_BWD_DATA))
-    ws = torch.full((nb + 4096,), 0xFF, dtype=torch.uint8, device=dev)
+    ws = guarded(dev, nb)
     shape = (N, K, d.P, d.Q) if fwd else (N, C, H, W)
     y = torch.full(shape, float('nan'), dtype=src.dtype, device=dev)
-    vp = ctypes.c_void_p
-    bp_ = vp(b.data_ptr()) if b is not None else vp(0)
-    st = vp(torch.cuda.current_stream().cuda_stream)
+    st = VP(torch.cuda.current_stream().cuda_stream)
     seq0, _ = _record()
     if fwd:
-        L.check(lib.pcgan_conv2d_fwd(ctypes.byref(d), vp(src.data_ptr()), vp(w.data_ptr()), bp_, vp(y.data_ptr()), c.act, T.SLOPE,
-                                     vp(ws.data_ptr()), nb, st), 'conv2d_fwd')
+        L.check(lib.pcgan_conv2d_fwd(ctypes.byref(d), ptr(src), ptr(w), ptr(b), ptr(y), c.act, T.SLOPE, ptr(ws), nb, st), 'conv2d_fwd')
     else:
-        L.check(lib.pcgan_conv2d_bwd_data(ctypes.byref(d), vp(src.data_ptr()), vp(w.data_ptr()), bp_, vp(y.data_ptr()), vp(ws.data_ptr()), nb, st),
-                'conv2d_bwd_data')
+        L.check(lib.pcgan_conv2d_bwd_data(ctypes.byref(d), ptr(src), ptr(w), ptr(b), ptr(y), ptr(ws), nb, st), 'conv2d_bwd_data')
     seq, rec = _record()
     assert seq == seq0 + 1, 'one recorded launch per call: %d after %d' % (seq, seq0)
     torch.cuda.synchronize()

@@ -26,8 +26,9 @@ Measured on an MI355X (256 CUs), recorded and not gated beyond the clauses above
     B      140    0                      0                      every element exact: 24 'xlow', 20 'wlow', 96 'fold' (8 source classes x 4 shapes x 3
                                                                 piece forms); v_mfma_f32_32x32x16_f16 and _bf16 add exactly when every partial sum is
                                                                 an fp32 number
-    C      148 launches of the maximum-slot cases (27 slot placements over 12 array lengths forward, 10 over 4 in the data gradient, x 4 alignments): exact
-           every time, counter at 0; 4 all-zero inputs and the 2 all-zero weight rows: exact; 12 range cases, relative L2 per channel
+    C      180 launches of the maximum-slot cases (33 slot placements over 12 array lengths forward, 12 over 4 in the data gradient, x 4 alignments;
+           from 8192 slots on also in the second and third of the four loads in flight): exact every time, counter at 0;
+           4 all-zero inputs and the 2 all-zero weight rows: exact; 12 range cases, relative L2 per channel
            7.0e-8 .. 3.1e-7 against 9.3e-8 .. 4.2e-7 on the fp32 route (wide_range 7.0e-8 .. 3.1e-7 | 9.3e-8 .. 3.0e-7, huge 1.3e-7 .. 2.9e-7 |
            2.1e-7 .. 4.1e-7, tiny 1.3e-7 .. 3.0e-7 | 2.1e-7 .. 4.2e-7); 4 four-corner cases: max |err| / bound 0.0008 .. 0.0028, relative L2
            1.5e-7 .. 1.8e-7
@@ -64,17 +65,12 @@ import pytest
 import torch
 
 import halo_cases as T
+from gpu_direct import VP, GUARD, ptr, guarded, where, coverage_gate
 
 pytestmark = pytest.mark.gpu
 
 NAMES = list(T.BY_NAME)
 SEEN = {}      # case name -> (section, (pass, piece form, width)) of the cases that ran in this process
-GUARD = 4096
-VP = ctypes.c_void_p
-
-
-def _ptr(t):
-    return VP(t.data_ptr()) if t is not None else VP(0)
 
 
 class _Call(object):
@@ -100,15 +96,15 @@ class _Call(object):
             assert self.lib.pcgan_conv2d_bsplit_dgrad_supported(ref) == 1
             self.nb = int(self.lib.pcgan_conv2d_bsplit_dgrad_packed_bytes(ref))
         assert self.nb == T.packed_bytes(c), (self.nb, T.packed_bytes(c))
-        self.pk = torch.full((self.nb + GUARD,), 0xFF, dtype=torch.uint8, device=dev)
+        self.pk = guarded(dev, self.nb)
         self.st = VP(torch.cuda.current_stream().cuda_stream)
         assert w.dtype == torch.float32 and w.is_contiguous()
         if c.pk == 'f16x2':
-            L.check(self.lib.pcgan_conv2d_hsplit_pack(ref, self.pass_, _ptr(w), _ptr(self.pk), self.st), 'conv2d_hsplit_pack')
+            L.check(self.lib.pcgan_conv2d_hsplit_pack(ref, self.pass_, ptr(w), ptr(self.pk), self.st), 'conv2d_hsplit_pack')
         elif c.pass_ == 'fwd':
-            L.check(self.lib.pcgan_conv2d_bsplit_pack(ref, _ptr(w), _ptr(self.pk), self.st), 'conv2d_bsplit_pack')
+            L.check(self.lib.pcgan_conv2d_bsplit_pack(ref, ptr(w), ptr(self.pk), self.st), 'conv2d_bsplit_pack')
         else:
-            L.check(self.lib.pcgan_conv2d_bsplit_dgrad_pack(ref, _ptr(w), _ptr(self.pk), self.st), 'conv2d_bsplit_dgrad_pack')
+            L.check(self.lib.pcgan_conv2d_bsplit_dgrad_pack(ref, ptr(w), ptr(self.pk), self.st), 'conv2d_bsplit_dgrad_pack')
 
     def run(self, src, b=None, add=None, maxima=None, act=0, slope=0.0):
         """the call into a NaN-filled view between two guards; returns the view (as float64 on the CPU too) after checking the guards"""
@@ -126,26 +122,26 @@ class _Call(object):
             if maxima is None:
                 slots = int(lib.pcgan_absmax_slots(src.numel()))
                 maxima = torch.full((slots,), float('nan'), device=self.dev)
-                L.check(lib.pcgan_absmax(_ptr(src), src.numel(), 0, _ptr(maxima), slots, self.st), 'absmax')
+                L.check(lib.pcgan_absmax(ptr(src), src.numel(), 0, ptr(maxima), slots, self.st), 'absmax')
             assert maxima.dtype == torch.float32 and maxima.is_contiguous()
             if c.pass_ == 'fwd':
                 assert add is None
-                L.check(lib.pcgan_conv2d_fwd_hsplit(ref, _ptr(src), _ptr(maxima), maxima.numel(), _ptr(self.pk), _ptr(b), _ptr(y), act, slope,
+                L.check(lib.pcgan_conv2d_fwd_hsplit(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(b), ptr(y), act, slope,
                                                     self.st), 'conv2d_fwd_hsplit')
             elif add is None:
                 assert b is None and act == 0
-                L.check(lib.pcgan_conv2d_bwd_data_hsplit(ref, _ptr(src), _ptr(maxima), maxima.numel(), _ptr(self.pk), _ptr(y), self.st),
+                L.check(lib.pcgan_conv2d_bwd_data_hsplit(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(y), self.st),
                         'conv2d_bwd_data_hsplit')
             else:
                 assert b is None and act == 0 and add.is_contiguous() and tuple(add.shape) == shape
-                L.check(lib.pcgan_conv2d_bwd_data_hsplit_add(ref, _ptr(src), _ptr(maxima), maxima.numel(), _ptr(self.pk), _ptr(add), _ptr(y),
+                L.check(lib.pcgan_conv2d_bwd_data_hsplit_add(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(add), ptr(y),
                                                              self.st), 'conv2d_bwd_data_hsplit_add')
         elif c.pass_ == 'fwd':
             assert add is None and maxima is None
-            L.check(lib.pcgan_conv2d_fwd_bsplit(ref, _ptr(src), _ptr(self.pk), _ptr(b), _ptr(y), act, slope, self.st), 'conv2d_fwd_bsplit')
+            L.check(lib.pcgan_conv2d_fwd_bsplit(ref, ptr(src), ptr(self.pk), ptr(b), ptr(y), act, slope, self.st), 'conv2d_fwd_bsplit')
         else:
             assert add is None and maxima is None and b is None and act == 0
-            L.check(lib.pcgan_conv2d_bwd_data_bsplit(ref, _ptr(src), _ptr(self.pk), _ptr(y), self.st), 'conv2d_bwd_data_bsplit')
+            L.check(lib.pcgan_conv2d_bwd_data_bsplit(ref, ptr(src), ptr(self.pk), ptr(y), self.st), 'conv2d_bwd_data_bsplit')
         torch.cuda.synchronize()
         assert bool((big[:GUARD] == 0xFF).all()) and bool((big[GUARD + nbytes:] == 0xFF).all()), 'the call wrote outside its output'
         assert bool((self.pk[self.nb:] == 0xFF).all()), 'the pack wrote behind the %d bytes it asked for' % self.nb
@@ -164,11 +160,6 @@ def _to(dev, c, t):
 def _dev(dev, c, d):
     f32 = lambda t: t.to(dev).contiguous() if t is not None else None
     return _to(dev, c, d.src), f32(d.w), f32(d.b), _to(dev, c, d.add)
-
-
-def _where(t):
-    i = int(t.flatten().argmax())
-    return tuple(int(v) for v in torch.unravel_index(torch.tensor(i), t.shape))
 
 
 def test_window_kernel_is_the_default_of_the_bsplit_entries():
@@ -198,10 +189,10 @@ def test_case(dev, name):
         (c.sect, name) + T.inst(c) + (ratio, rel, int((yc != want).sum()))))
     if c.kind == 'signed':
         assert bool((err <= bound).all()), '%d element(s) outside the bound, worst %.3g x the bound at %r' % (
-            int((err > bound).sum()), ratio, _where(err / bound.clamp_min(1e-300)))
+            int((err > bound).sum()), ratio, where(err / bound.clamp_min(1e-300)))
     else:
         assert bool((yc == want).all()), '%d element(s) not exact, the first worst at %r: %r, reference %r' % (
-            int((yc != want).sum()), _where(err), float(yc[_where(err)]), float(want[_where(err)]))
+            int((yc != want).sum()), where(err), float(yc[where(err)]), float(want[where(err)]))
 
 
 # ---- C. scales and ranges (f16x2) --------------------------------------------------------------------------------------------------------
@@ -209,7 +200,8 @@ def test_case(dev, name):
 def test_maximum_in_every_slot(dev, pass_, n):
     """sx comes from thread_max_of_partials (512 threads) over a maxima array of the caller's making: the true maximum (2^15 - 1 forward,
     2^13 - 1 in the data gradient; every other magnitude and every other slot is 16) in the first slot, the last, the last lane of the
-    first 4-in-flight round and the last float4, with the array 0, 4, 8 and 12 bytes off a 16-byte boundary.  A missed slot scales the
+    first 4-in-flight round, the second and the third load in flight and the last float4 (split_arith.maxima_slots), with the array 0, 4, 8
+    and 12 bytes off a 16-byte boundary.  A missed slot scales the
     pinned element past fp16: the result is not the exact one and the non-finite counter moves.  (The data gradient shares the code:
     four lengths.)"""
     c = T.MAXPOS[pass_]
@@ -314,16 +306,10 @@ def test_four_corner_sums_stay_in_fp16(dev, width, which):
     y, yc = _Call(dev, c, w.to(dev).contiguous()).run(dy.to(dev).contiguous())
     err = (yc - want).abs()
     print('HALO C corner %d %s: max |err| / bound %.4f, relative L2 %.3e' % (width, which, float((err / bound).max()), float((yc - want).norm() / want.norm())))
-    assert bool((err <= bound).all()), '%d element(s) outside the bound, the worst at %r' % (int((err > bound).sum()), _where(err / bound))
+    assert bool((err <= bound).all()), '%d element(s) outside the bound, the worst at %r' % (int((err > bound).sum()), where(err / bound))
 
 
 def test_zz_every_instantiation_ran():
     """from the cases that ran in this process: all twelve instantiations in section A and in section B, when the whole file ran.  A
     selection (-k, one worker of several) is held to its own cases only; a process in which no case ran has nothing to check and says so"""
-    assert SEEN, 'no case of this file ran in this process before this test: nothing was checked (run the whole file in one process)'
-    for i in T.INSTANTIATIONS:
-        print('COVERAGE %-5s %-6s W %d: A %2d case(s), B %2d' % (i + tuple(sum(1 for s in SEEN.values() if s == (sect, i)) for sect in 'AB')))
-    assert {s for s in SEEN.values()} == {(T.BY_NAME[n].sect, T.inst(T.BY_NAME[n])) for n in SEEN}
-    if len(SEEN) == len(NAMES):
-        for sect in 'AB':
-            assert {s[1] for s in SEEN.values() if s[0] == sect} == set(T.INSTANTIATIONS), 'section %s: an instantiation no case reached' % sect
+    coverage_gate(SEEN, NAMES, T.INSTANTIATIONS, 'AB', T.BY_NAME, T.inst, 'COVERAGE %-5s %-6s W %d: A %2d case(s), B %2d')

@@ -76,17 +76,12 @@ import pytest
 import torch
 
 import hgemm_cases as T
+from gpu_direct import VP, GUARD, ptr, guarded, where, bits, coverage_gate
 
 pytestmark = pytest.mark.gpu
 
 NAMES = list(T.BY_NAME)
 SEEN = {}      # case name -> (section, instantiation) of the cases that ran in this process
-GUARD = 4096
-VP = ctypes.c_void_p
-
-
-def _ptr(t):
-    return VP(t.data_ptr()) if t is not None else VP(0)
 
 
 @pytest.fixture
@@ -107,11 +102,6 @@ def force():
         ops.clear_plans()
 
 
-def _guarded(dev, nbytes):
-    """nbytes of 0xFF with a 0xFF tail behind them"""
-    return torch.full((nbytes + GUARD,), 0xFF, dtype=torch.uint8, device=dev)
-
-
 class _Call(object):
     """one packed weight tensor and the buffers of a direct call under the options as they stand, guards included"""
 
@@ -129,14 +119,14 @@ class _Call(object):
         self.wsb = int(self.lib.pcgan_conv2d_workspace_bytes(ref, self.pass_))
         image = 4 * sum(self.M * p.Kp for p in T.hgemm_plan(c).phases)
         assert self.nb >= image and self.wsb >= self.nb
-        self.pk, self.ws, self.rm = _guarded(dev, self.nb), _guarded(dev, self.wsb), _guarded(dev, 4 * self.M)
+        self.pk, self.ws, self.rm = guarded(dev, self.nb), guarded(dev, self.wsb), guarded(dev, 4 * self.M)
         self.rowmax = self.rm[:4 * self.M].view(torch.float32)
         self.st = VP(torch.cuda.current_stream().cuda_stream)
         assert w.dtype == torch.float32 and w.is_contiguous()
         if c.half:
-            L.check(self.lib.pcgan_conv2d_pack_weights(ref, self.pass_, _ptr(w), _ptr(self.pk), self.st), 'conv2d_pack_weights')
+            L.check(self.lib.pcgan_conv2d_pack_weights(ref, self.pass_, ptr(w), ptr(self.pk), self.st), 'conv2d_pack_weights')
         else:
-            L.check(self.lib.pcgan_conv2d_hgemm_pack(ref, self.pass_, _ptr(w), _ptr(self.rowmax), _ptr(self.pk), self.st), 'conv2d_hgemm_pack')
+            L.check(self.lib.pcgan_conv2d_hgemm_pack(ref, self.pass_, ptr(w), ptr(self.rowmax), ptr(self.pk), self.st), 'conv2d_hgemm_pack')
 
     def run(self, src, b=None, maxima=None, act=0, slope=0.0, want=None):
         """the call into a NaN-filled view between two guards; returns the view (as float64 on the CPU too) after checking the guards,
@@ -156,21 +146,21 @@ class _Call(object):
             if maxima is None:
                 slots = int(lib.pcgan_absmax_slots(src.numel()))
                 maxima = torch.full((slots,), float('nan'), device=self.dev)
-                L.check(lib.pcgan_absmax(_ptr(src), src.numel(), 0, _ptr(maxima), slots, self.st), 'absmax')
+                L.check(lib.pcgan_absmax(ptr(src), src.numel(), 0, ptr(maxima), slots, self.st), 'absmax')
             assert maxima.dtype == torch.float32 and maxima.is_contiguous()
             if c.pass_ == 'fwd':
-                L.check(lib.pcgan_conv2d_fwd_packed_hsplit(ref, _ptr(src), _ptr(maxima), maxima.numel(), _ptr(self.pk), _ptr(self.rowmax), _ptr(b),
-                                                           _ptr(y), act, slope, _ptr(self.ws), self.wsb, self.st), 'conv2d_fwd_packed_hsplit')
+                L.check(lib.pcgan_conv2d_fwd_packed_hsplit(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(self.rowmax), ptr(b),
+                                                           ptr(y), act, slope, ptr(self.ws), self.wsb, self.st), 'conv2d_fwd_packed_hsplit')
             else:
                 assert act == 0
-                L.check(lib.pcgan_conv2d_bwd_data_packed_hsplit(ref, _ptr(src), _ptr(maxima), maxima.numel(), _ptr(self.pk), _ptr(self.rowmax),
-                                                                _ptr(b), _ptr(y), _ptr(self.ws), self.wsb, self.st), 'conv2d_bwd_data_packed_hsplit')
+                L.check(lib.pcgan_conv2d_bwd_data_packed_hsplit(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(self.rowmax),
+                                                                ptr(b), ptr(y), ptr(self.ws), self.wsb, self.st), 'conv2d_bwd_data_packed_hsplit')
         elif c.pass_ == 'fwd':
-            L.check(lib.pcgan_conv2d_fwd_packed(ref, _ptr(src), _ptr(self.pk), _ptr(b), _ptr(y), act, slope, _ptr(self.ws), self.wsb, self.st),
+            L.check(lib.pcgan_conv2d_fwd_packed(ref, ptr(src), ptr(self.pk), ptr(b), ptr(y), act, slope, ptr(self.ws), self.wsb, self.st),
                     'conv2d_fwd_packed')
         else:
             assert act == 0
-            L.check(lib.pcgan_conv2d_bwd_data_packed(ref, _ptr(src), _ptr(self.pk), _ptr(b), _ptr(y), _ptr(self.ws), self.wsb, self.st),
+            L.check(lib.pcgan_conv2d_bwd_data_packed(ref, ptr(src), ptr(self.pk), ptr(b), ptr(y), ptr(self.ws), self.wsb, self.st),
                     'conv2d_bwd_data_packed')
         torch.cuda.synchronize()
         rec = ops.igemm_last_launch()
@@ -193,15 +183,6 @@ def _dev(dev, c, d):
     src = d.src.to(dev).to(dt).contiguous()
     assert bool((src.double().cpu() == d.src.double()).all()), 'the operand is no number of the storage type'
     return src, d.w.to(dev).contiguous(), (d.b.to(dev).contiguous() if d.b is not None else None)
-
-
-def _where(t):
-    i = int(t.flatten().argmax())
-    return tuple(int(v) for v in torch.unravel_index(torch.tensor(i), t.shape))
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
 
 
 def _through_ops(c, src, w, b):
@@ -242,19 +223,19 @@ def test_case(dev, force, name):
         (c.sect, name) + T.inst(c) + (pl.ks, ratio, rel, int((yc != want).sum()))))
     if c.kind == 'signed':
         assert bool((err <= bound).all()), '%d element(s) outside the bound, worst %.3g x the bound at %r' % (
-            int((err > bound).sum()), ratio, _where(err / bound.clamp_min(1e-300)))
+            int((err > bound).sum()), ratio, where(err / bound.clamp_min(1e-300)))
         if pl.need_zero:
             un = d.A == 0
             assert bool(un.any()) and bool((yc[un] == 0).all()) and not bool(torch.signbit(yc[un]).any()), 'a pixel no phase writes is not +0'
     else:
         assert bool((yc == want).all()), '%d element(s) not exact, the first worst at %r: %r, reference %r' % (
-            int((yc != want).sum()), _where(err), float(yc[_where(err)]), float(want[_where(err)]))
+            int((yc != want).sum()), where(err), float(yc[where(err)]), float(want[where(err)]))
     seq0 = ops.igemm_last_launch()['seq']
     y2, routes = _through_ops(c, src, w, b)
     assert routes == {(c.pass_, 'packed' if c.half else 'hgemm'): 1}, routes
     rec = ops.igemm_last_launch()
     assert rec['seq'] == seq0 + 1 and (rec['form'], rec['mode'], rec['bm'], rec['bp'], rec['ks'], rec['nphase']) == c.want, rec
-    assert torch.equal(_bits(y2), _bits(y)), 'the production path differs from the direct call in %d element(s)' % int((_bits(y2) != _bits(y)).sum())
+    assert torch.equal(bits(y2), bits(y)), 'the production path differs from the direct call in %d element(s)' % int((bits(y2) != bits(y)).sum())
 
 
 @pytest.mark.parametrize('i', range(len(T.NEED_ZERO_REFUSED)))
@@ -418,8 +399,8 @@ def test_pack_bytes(dev, i):
     nb = int(lib.pcgan_conv2d_packed_bytes(ref, pass_))
     raw, rowmax = T.packed_presplit(c, w)
     assert raw.numel() <= nb
-    pk, rm = _guarded(dev, nb), _guarded(dev, 4 * M)
-    L.check(lib.pcgan_conv2d_hgemm_pack(ref, pass_, _ptr(w.to(dev).contiguous()), _ptr(rm), _ptr(pk), VP(torch.cuda.current_stream().cuda_stream)),
+    pk, rm = guarded(dev, nb), guarded(dev, 4 * M)
+    L.check(lib.pcgan_conv2d_hgemm_pack(ref, pass_, ptr(w.to(dev).contiguous()), ptr(rm), ptr(pk), VP(torch.cuda.current_stream().cuda_stream)),
             'conv2d_hgemm_pack')
     torch.cuda.synchronize()
     got = pk.cpu()
@@ -434,13 +415,6 @@ def test_pack_bytes(dev, i):
 def test_zz_every_instantiation_ran():
     """from the cases that ran in this process: all 24 instantiations in section A and in section B, when the whole file ran.  A
     selection (-k, one worker of several) is held to its own cases only; a process in which no case ran has nothing to check and says so"""
-    assert SEEN, 'no case of this file ran in this process before this test: nothing was checked (run the whole file in one process)'
-    for i in T.INSTANTIATIONS:
-        print('COVERAGE %-11s %3d x %3d %s: A %2d case(s), B %2d' % (i + tuple(sum(1 for s in SEEN.values() if s == (sect, i)) for sect in 'AB')))
-    assert {s for s in SEEN.values()} == {(T.BY_NAME[n].sect, T.inst(T.BY_NAME[n])) for n in SEEN}
-    if len(SEEN) == len(NAMES):
-        for sect in 'AB':
-            assert {s[1] for s in SEEN.values() if s[0] == sect} == set(T.INSTANTIATIONS), 'section %s: an instantiation no case reached' % sect
-    else:
+    if not coverage_gate(SEEN, NAMES, T.INSTANTIATIONS, 'AB', T.BY_NAME, T.inst, 'COVERAGE %-11s %3d x %3d %s: A %2d case(s), B %2d'):
         print('COVERAGE not gated: %d of %d cases ran in this process; the 24-instantiation gate applies when the whole file runs in one process' % (
             len(SEEN), len(NAMES)))

@@ -35,11 +35,11 @@ Measured on an MI355X (256 CUs), max(|err| / bound) and relative L2 error per gr
   any lost, doubled or misplaced term is >= 2 x the bound.
   Wall time of the module: 2.5 s for its 253 tests (the slowest 1.1 s: the first, which loads the library; every other under 0.1 s)."""
 import ctypes
-import functools
 
 import pytest
 import torch
 
+import gpu_direct as D
 import hsplit_wgrad_cases as H
 
 pytestmark = pytest.mark.gpu
@@ -95,8 +95,8 @@ def _launch(dev, geom, half, x, dy, base, maxima, seed=0):
     d = _desc(geom, half)
     assert lib.pcgan_conv2d_hsplit_wgrad_supported(ctypes.byref(d))
     nb = int(lib.pcgan_conv2d_hsplit_wgrad_workspace_bytes(ctypes.byref(d)))
-    ws = torch.empty((nb + 4096,), dtype=torch.uint8, device=dev)
-    vp = ctypes.c_void_p
+    ws = D.guarded(dev, nb)
+    vp = D.VP
     xd, dyd = x.to(dev).contiguous(), dy.to(dev).contiguous()
     if half:
         mx = (None, 0, None, 0)
@@ -161,26 +161,6 @@ def test_exact(dev, case, library_options):
 
 
 # ---- C: operand ranges ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _range_case(kind, geom):
-    """(x, dy, float64 reference) of one operand-range case: the four kinds of tests/test_gpu_wgrad_rowring.py"""
-    N, C, Hh, W, K, Rr, S, st, pad, pm = geom
-    P, Q = H.out_size(Hh, Rr, st, pad), H.out_size(W, S, st, pad)
-    g = torch.Generator().manual_seed(N + C + K + Hh + W)
-    x = torch.randn(N, C, Hh, W, generator=g)
-    dy = torch.randn(N, K, P, Q, generator=g)
-    if kind == 'relu_normal':
-        x, dy = x.relu_(), dy * 0.05
-    elif kind == 'wide_range':
-        x = x * torch.pow(10.0, torch.rand(N, C, Hh, W, generator=g) * 8 - 6)
-        dy = dy * torch.pow(10.0, torch.rand(N, K, P, Q, generator=g) * 12 - 14)
-    elif kind == 'tiny':
-        x, dy = x * 1e-30, dy * 1e-4
-    else:
-        x, dy = x * 1e12, dy * 1e8
-    return x, dy, H.grad64(x, dy, geom)
-
-
 def _fp32_route(x, dy, geom):
     """the project's fp32 route (the fp32-MFMA weight gradient) on the same device tensors"""
     from pcgan_amd.hip import ops
@@ -202,15 +182,11 @@ def _fp32_route(x, dy, geom):
     return dw32.double().cpu()
 
 
-def _errors(t, ref):
-    return float((t - ref).norm() / ref.norm()), float((t - ref).abs().max() / ref.abs().max())
-
-
 @pytest.mark.parametrize('maxima', ['plane', 'amax_of'])
 @pytest.mark.parametrize('kind', H.C_KINDS)
 @pytest.mark.parametrize('geom', H.C_SHAPES, ids=['gen', 'reflect'])
 def test_operand_ranges(dev, geom, kind, maxima, library_options):
-    x, dy, ref = _range_case(kind, geom)
+    x, dy, ref = D.range_case(kind, geom, H.grad64)
     library_options({})
     pl = H.plan(geom, False, {})
     K, C, Rr, S = geom[4], geom[1], geom[5], geom[6]
@@ -220,7 +196,7 @@ def test_operand_ranges(dev, geom, kind, maxima, library_options):
     assert tuple(rec[k] for k in H.RECORD) == H.record(pl), rec
     dw32 = _fp32_route(x.to(dev), dy.to(dev), geom)
     out = dw.double().cpu()
-    (e, m), (e32, m32) = _errors(out, ref), _errors(dw32, ref)
+    (e, m), (e32, m32) = D.errors(out, ref), D.errors(dw32, ref)
     print('HWGRAD C %s %s %s: relative L2 (e, e32) = (%.3e, %.3e); max|err| / max|ref| (per-tap, fp32 route) = (%.3e, %.3e)' % (geom, kind, maxima, e, e32, m, m32))
     assert bool(torch.isfinite(out).all())
     assert e < 3e-6 and e <= 2 * e32 + 5e-7, 'relative L2 %.3e (fp32 route %.3e)' % (e, e32)

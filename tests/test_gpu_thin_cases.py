@@ -26,7 +26,8 @@ Measured on an MI355X (256 CUs), recorded and not gated beyond the clauses above
     B       14    0                     0                      every element exact, 'xlow' and 'wlow', all six (kernel, form) pairs: the
                                                                premise that v_mfma_f32_32x32x16_f16 adds exactly when every partial sum is an
                                                                fp32 number holds on this chip
-    C      108 launches of the maximum-slot case (27 slot placements x 4 alignments, 12 array lengths): exact every time, sentinel at 0;
+    C      132 launches of the maximum-slot case (33 slot placements x 4 alignments, 12 array lengths; from 4096 slots on also in the second
+           and third of the four loads in flight): exact every time, sentinel at 0;
            4 all-zero inputs and the two all-zero filter rows: exact; 6 range cases: relative L2 per channel 8.4e-8 .. 2.0e-7 against
            5.8e-8 .. 2.8e-7 on the fp32-MFMA route (wide_range 8.4e-8 .. 2.0e-7, huge 1.3e-7 .. 2.0e-7, tiny 1.3e-7 .. 1.9e-7)
   The bound of section A is a worst case over orders and signs, so the errors sit far inside it; what the gate buys is the condition: a
@@ -54,12 +55,12 @@ import pytest
 import torch
 
 import thin_cases as T
+from gpu_direct import VP, GUARD, ptr, guarded, where
 
 pytestmark = pytest.mark.gpu
 
 NAMES = list(T.BY_NAME)
 SEEN = {}      # case name -> (kernel, form, M / 64, gathered channels) of the cases that ran in this process
-GUARD = 4096
 
 
 class _Call(object):
@@ -75,15 +76,13 @@ class _Call(object):
         self.nb = int(self.lib.pcgan_conv2d_thin_packed_bytes(ref, self.pass_))
         self.nws = int(self.lib.pcgan_conv2d_thin_workspace_bytes(ref, self.pass_))
         assert self.nb == T.packed_bytes(c) and self.nws == T.workspace_bytes(c)
-        self.pk = torch.full((self.nb + GUARD,), 0xFF, dtype=torch.uint8, device=dev)
-        self.ws = torch.full((self.nws + GUARD,), 0xFF, dtype=torch.uint8, device=dev)
-        self.st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        vp = ctypes.c_void_p
-        L.check(self.lib.pcgan_conv2d_thin_pack(ref, self.pass_, vp(w.data_ptr()), vp(self.pk.data_ptr()), self.st), 'conv2d_thin_pack')
+        self.pk, self.ws = guarded(dev, self.nb), guarded(dev, self.nws)
+        self.st = VP(torch.cuda.current_stream().cuda_stream)
+        L.check(self.lib.pcgan_conv2d_thin_pack(ref, self.pass_, ptr(w), ptr(self.pk), self.st), 'conv2d_thin_pack')
 
     def run(self, src, b, maxima, act, slope):
         """the call into a NaN-filled view between two guards; returns the view after checking every guard"""
-        c, vp = self.c, ctypes.c_void_p
+        c = self.c
         shape = T.out_shape(c)
         nbytes = 4 * shape[0] * shape[1] * shape[2] * shape[3]
         big = torch.full((nbytes + 2 * GUARD,), 0xFF, dtype=torch.uint8, device=self.dev)
@@ -92,13 +91,12 @@ class _Call(object):
         assert maxima.dtype == torch.float32 and maxima.is_contiguous() and src.is_contiguous()
         ref = ctypes.byref(self.d)
         if c.pass_ == 'fwd':
-            self.L.check(self.lib.pcgan_conv2d_fwd_thin(ref, vp(src.data_ptr()), vp(maxima.data_ptr()), maxima.numel(), vp(self.pk.data_ptr()),
-                                                        vp(b.data_ptr()) if b is not None else vp(0), vp(y.data_ptr()), act, slope, self.st),
+            self.L.check(self.lib.pcgan_conv2d_fwd_thin(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(b), ptr(y), act, slope, self.st),
                          'conv2d_fwd_thin')
         else:
             assert b is None and act == 0
-            self.L.check(self.lib.pcgan_conv2d_bwd_data_thin(ref, vp(src.data_ptr()), vp(maxima.data_ptr()), maxima.numel(), vp(self.pk.data_ptr()),
-                                                             vp(y.data_ptr()), vp(self.ws.data_ptr()), self.nws, self.st), 'conv2d_bwd_data_thin')
+            self.L.check(self.lib.pcgan_conv2d_bwd_data_thin(ref, ptr(src), ptr(maxima), maxima.numel(), ptr(self.pk), ptr(y), ptr(self.ws), self.nws,
+                                                             self.st), 'conv2d_bwd_data_thin')
         torch.cuda.synchronize()
         assert bool((big[:GUARD] == 0xFF).all()) and bool((big[GUARD + nbytes:] == 0xFF).all()), 'the call wrote outside its output'
         assert bool((self.pk[self.nb:] == 0xFF).all()), 'the pack wrote behind the %d bytes it asked for' % self.nb
@@ -129,11 +127,6 @@ def _dev(dev, d):
     return d.src.to(dev).contiguous(), d.w.to(dev).contiguous(), (d.b.to(dev).contiguous() if d.b is not None else None)
 
 
-def _where(t):
-    i = int(t.flatten().argmax())
-    return tuple(int(v) for v in torch.unravel_index(torch.tensor(i), t.shape))
-
-
 @pytest.mark.parametrize('name', NAMES)
 def test_case(dev, name):
     c = T.BY_NAME[name]
@@ -158,10 +151,10 @@ def test_case(dev, name):
     assert finite, 'elements nobody wrote: %d' % int((~torch.isfinite(yc)).sum())
     if c.kind == 'signed':
         assert bool((err <= bound).all()), '%d element(s) outside the bound, worst %.3g x the bound at %r' % (
-            int((err > bound).sum()), ratio, _where(err / bound.clamp_min(1e-300)))
+            int((err > bound).sum()), ratio, where(err / bound.clamp_min(1e-300)))
     else:
         assert bool((yc == aref).all()), '%d element(s) not exact, the first worst at %r: %r, reference %r' % (
-            int((yc != aref).sum()), _where(err), float(yc[_where(err)]), float(aref[_where(err)]))
+            int((yc != aref).sum()), where(err), float(yc[where(err)]), float(aref[where(err)]))
     y2 = _through_ops(c, src, w, b)
     assert torch.equal(y2, y), 'direct and pack-cache calls differ in %d element(s)' % int((y2 != y).sum())
 
@@ -170,7 +163,8 @@ def test_case(dev, name):
 @pytest.mark.parametrize('n', T.MAXPOS_N)
 def test_maximum_in_every_slot(dev, n):
     """sx comes from thread_max_of_partials over a maxima array of the caller's making: the true maximum (2^15 - 1; every other magnitude and
-    every other slot is 16) in the first slot, the last, the last lane of the 4-in-flight float4 loop and the last float4, with the array 0,
+    every other slot is 16) in the first slot, the last, the last lane of the 4-in-flight float4 loop, its second and third load and the last
+    float4 (split_arith.maxima_slots), with the array 0,
     4, 8 and 12 bytes off a 16-byte boundary.  A missed slot scales 32767 by 2^9: fp16 overflows, the result is not the exact one and the
     non-finite sentinel counts it"""
     from pcgan_amd.hip import ops

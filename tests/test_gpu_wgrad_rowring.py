@@ -30,6 +30,7 @@ import functools
 import pytest
 import torch
 
+import gpu_direct as D
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -45,22 +46,9 @@ def _reference(x, dy, K, C):
     return w.grad.detach()
 
 
-@functools.lru_cache(maxsize=None)
-def _range_case(kind, N, C, K, H, W):
-    """(x, dy, float64 reference) of one operand-range case on the CPU: made once, shared by the tests that use it, never written to"""
-    g = torch.Generator().manual_seed(N + C + K + H + W)
-    x = torch.randn(N, C, H, W, generator=g)
-    dy = torch.randn(N, K, H, W, generator=g)
-    if kind == 'relu_normal':
-        x, dy = x.relu_(), dy * 0.05
-    elif kind == 'wide_range':         # magnitudes over eight / twelve decades inside one tensor
-        x = x * torch.pow(10.0, torch.rand(N, C, H, W, generator=g) * 8 - 6)
-        dy = dy * torch.pow(10.0, torch.rand(N, K, H, W, generator=g) * 12 - 14)
-    elif kind == 'tiny':               # products near 1e-34: normal fp32, but sx sits at the +100 clamp and 1 / (sx sdy) at the edge of the normal range
-        x, dy = x * 1e-30, dy * 1e-4
-    else:                              # true values near 1e21
-        x, dy = x * 1e12, dy * 1e8
-    return x, dy, _reference(x, dy, K, C)
+def _reference64(x, dy, geom):
+    """_reference by the geometry: the reference of gpu_direct.range_case"""
+    return _reference(x, dy, geom[4], geom[1])
 
 
 @functools.lru_cache(maxsize=None)
@@ -127,12 +115,8 @@ def _fp32_route(x, dy, K, C):
     return dw32.double().cpu()
 
 
-def _errors(t, ref):
-    return float((t - ref).norm() / ref.norm()), float((t - ref).abs().max() / ref.abs().max())
-
-
 def _check_fp32(what, dw, acc, dw32, ref):
-    (e, m), (e32, m32), (ea, _) = _errors(dw, ref), _errors(dw32, ref), _errors(acc, ref)
+    (e, m), (e32, m32), (ea, _) = D.errors(dw, ref), D.errors(dw32, ref), D.errors(acc, ref)
     print('%s: relative L2 (e, e32) = (%.3e, %.3e); max|err| / max|ref| (row ring, fp32 route) = (%.3e, %.3e); accumulate %.3e' % (what, e, e32, m, m32, ea))
     assert torch.isfinite(dw).all(), what
     assert e < 3e-6 and e <= 2 * e32 + 5e-7, '%s: relative L2 %.3e (fp32 route %.3e)' % (what, e, e32)
@@ -148,7 +132,7 @@ def test_row_ring_operand_ranges(dev, N, C, K, H, W, kind, maxima):
     """fp32 tensors whose magnitudes drive the operand scaling, its exponent clamp and the scale-back of the reduce; the operand maxima
     both ways the product hands them over: one slot per plane (as the instance-norm kernels do) and the tensor of ops.amax_of."""
     from pcgan_amd.hip import ops
-    x, dy, ref = _range_case(kind, N, C, K, H, W)
+    x, dy, ref = D.range_case(kind, (N, C, H, W, K, 3, 3, 1, 1, 1), _reference64)
     # the reference itself is a fair fp32 target: its largest 99 % (by magnitude) lie inside fp32's normal range
     mags = ref.abs().flatten().sort().values
     assert float(mags[mags.numel() // 100]) >= 2.0 ** -126 and float(mags[-1]) < 2.0 ** 127
@@ -223,7 +207,7 @@ def test_row_ring_multi_strip_walk_bf16(dev, walk, H):
     N, C, K, W = _walk(dev, walk, H, True)
     x, dy, ref = _walk_case(N, C, K, H, W, True)
     dw, acc = _rowring(dev, x.to(dev), dy.to(dev), ref, None, N + H)
-    (e, m), (ea, _) = _errors(dw, ref), _errors(acc, ref)
+    (e, m), (ea, _) = D.errors(dw, ref), D.errors(acc, ref)
     print('%s H=%d bf16: relative L2 %.3e; max|err| / max|ref| %.3e; accumulate %.3e' % (walk, H, e, m, ea))
     assert torch.isfinite(dw).all()
     assert e < 1e-6, e

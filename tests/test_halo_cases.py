@@ -184,7 +184,10 @@ def test_corner_sums_need_the_saturating_split(width, which):
 def test_maxima_slots():
     assert T.maxima_slots(1) == [0] and T.maxima_slots(5) == [0, 4] and T.maxima_slots(2047) == [0, 2046]
     assert T.maxima_slots(2048) == [0, 2047] and T.maxima_slots(2049) == [0, 2047, 2048]
-    assert T.maxima_slots(8192) == [0, 8191] and T.maxima_slots(8200) == [0, 8191, 8199] and T.maxima_slots(8203) == [0, 8191, 8199, 8202]
+    mid = [4 * T.NT + 1, 4 * (2 * T.NT + 77) + 2]      # float4 NT (thread 0's second load) and 2 NT + 77 (thread 77's third load)
+    assert T.maxima_slots(8192) == [0] + mid + [8191] and T.maxima_slots(8200) == [0] + mid + [8191, 8199]
+    assert T.maxima_slots(8203) == [0] + mid + [8191, 8199, 8202]
+    assert mid == [2049, 4406] and mid[0] // 4 == T.NT and mid[1] // 4 == 2 * T.NT + 77 and 77 + 3 * T.NT < 8192 // 4
     # 8192 slots = 2048 float4: every thread of 512 runs the 4-in-flight loop once (i + 3 * 512 < 2048) and float4 2047 is its last load;
     # 8200: float4 2048 and 2049 fall to the remainder loop; 8203: three elements to the scalar tail
     assert 2048 // 4 == T.NT and (8200 // 4) - 4 * T.NT == 2 and 8203 - 4 * (8203 // 4) == 3

@@ -109,7 +109,10 @@ def test_emulation_is_exact_and_notices_one_piece(name):
 def test_maxima_slots():
     assert T.maxima_slots(1) == [0] and T.maxima_slots(5) == [0, 4] and T.maxima_slots(1023) == [0, 1022]
     assert T.maxima_slots(1024) == [0, 1023] and T.maxima_slots(1025) == [0, 1023, 1024]
-    assert T.maxima_slots(4096) == [0, 4095] and T.maxima_slots(4100) == [0, 4095, 4099] and T.maxima_slots(4103) == [0, 4095, 4099, 4102]
+    mid = [4 * T.NT + 1, 4 * (2 * T.NT + 77) + 2]      # float4 NT (thread 0's second load) and 2 NT + 77 (thread 77's third load)
+    assert T.maxima_slots(4096) == [0] + mid + [4095] and T.maxima_slots(4100) == [0] + mid + [4095, 4099]
+    assert T.maxima_slots(4103) == [0] + mid + [4095, 4099, 4102]
+    assert mid == [1025, 2358] and mid[0] // 4 == T.NT and mid[1] // 4 == 2 * T.NT + 77 and 77 + 3 * T.NT < 4096 // 4
 
 
 # ---- section D: the predicates ---------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ Host forms: fwd_zero, fwd_reflect, dgrad_zero (a forward-form convolution of dy 
 (the same on the padded grid (H + 2 pad) x (W + 2 pad) into the workspace, then reflect_fold_kernel).
 
 Section A, kind 'signed' (conv_f32_cases._signed): |x|, |w|, |dy|, |bias| in [0.75, 1.25] with random signs; the tanh / sigmoid cases
-multiply the weights by 2^-4 (`wexp`) so that |ref| stays near 1.  Reference: conv_f32_cases._fwd64 / _dgrad64 (float64, autograd through
+multiply the weights by 2^-4 (`wexp`) so that |ref| stays near 1.  Reference: split_arith.reference (float64, autograd through
 the reflection: it sums the mirror images); the same call on absolute values gives A.  Per element
     |y - ref| <= E = (2 (3 Kp + 8) 2^-24 + 2^-20) A,      Kp = 16 NST = 208 (7x7) | 64 (4x4)
 Each scaled operand splits as h + l with relative error <= 2^-22; the dropped (l,l) product is <= 2^-22 of the term; with the second-order
@@ -34,15 +34,16 @@ shifted.
 Section C data (ranges): `range_data` -- randn as in tests/test_gpu_thin.py, the kinds of tests/test_gpu_wgrad_rowring.py."""
 import collections
 import functools
-import math
 
 import torch
 
 from oracle import ops_ref as R
-from conv_f32_cases import _signed, _fwd64, _dgrad64, out_size, TERM_MIN, SLOPE
+import split_arith
+from conv_f32_cases import _signed, TERM_MIN
+# (SLOPE, per_row_rel: the tests reach them through this module)
+from split_arith import U, SLOPE, out_size, _ints, _fwd64, _dgrad64, pow2_scale, split2h, per_row_rel, range_scale
 
-U = 2.0 ** -24
-SLOPE_EXACT = 0.25
+NT = 256                        # threads of a workgroup (thread_max_of_partials strides by it)
 TH, TW = 8, 32                  # the workgroup's tile of output pixels
 KERNELS = ('<7,7,1>', '<7,7,2>', '<4,4,2>')
 # every (kernel, host form) pair the library accepts: reflection and the data gradient are stride 1, 7x7
@@ -144,10 +145,6 @@ CLAIMS = {
 
 
 # ---- data, reference, bound --------------------------------------------------------------------------------------------------------------------
-def _ints(g, lo, hi, shape):
-    return torch.randint(lo, hi + 1, shape, generator=g).float()
-
-
 @functools.lru_cache(maxsize=None)
 def data(c):
     """(src, w, bias, float64 reference BEFORE the activation, A, row exponents) of a case on the CPU: made once, shared, never written to"""
@@ -182,13 +179,11 @@ def data(c):
 
 def reference(c, src, w, b):
     """(float64 result before the activation, the same call on absolute values) of the case's geometry on the given operands"""
-    f = _fwd64 if c.pass_ == 'fwd' else _dgrad64
-    s64, w64, b64 = src.double(), w.double(), (b.double() if b is not None else None)
-    return f(s64, w64, b64, c.geom), f(s64.abs(), w64.abs(), b64.abs() if b is not None else None, c.geom)
+    return split_arith.reference(c.pass_, c.geom, src, w, b)
 
 
 def slope_of(c):
-    return SLOPE if c.kind == 'signed' else SLOPE_EXACT
+    return split_arith.slope_of(c.kind)
 
 
 def bounds(c, A=None, ref=None):
@@ -208,29 +203,10 @@ def condition(c):
 
 def quanta(c):
     """exact kinds: the largest A of the case in units of its quantum (1 for 'xlow'; 2^j of the row for 'wlow'); must stay under 2^24"""
-    d = data(c)
-    if d.rowexp is None:
-        return float(d.A.max())
-    return float((d.A / torch.pow(2.0, d.rowexp.double()).view(1, -1, 1, 1)).max())
+    return split_arith.quanta(data(c))
 
 
 # ---- the kernel's arithmetic in torch --------------------------------------------------------------------------------------------------------
-def pow2_scale(amax):
-    """common.h: the power of two that puts amax into [2^13, 2^14); 1 for 0; exponent clamped to +-100"""
-    if not amax > 0.0:
-        return 1.0
-    e = 14 - math.frexp(amax)[1]
-    return 2.0 ** max(-100, min(100, e))
-
-
-def split2h(x):
-    """fp32 tensor -> (h, l) fp16 pieces as fp32 tensors; the split must not overflow fp16"""
-    h = x.half()
-    l = (x - h.float()).half()
-    assert bool(torch.isfinite(h).all())
-    return h.float(), l.float()
-
-
 def emulate(c, perturb=None):
     """scale, split, the three piece products (l,h) (h,l) (h,h) each summed exactly and accumulated in fp32, scale back with the two
     reciprocals, bias, activation -- as float64 for the comparison.  perturb: 'zero_xl' / 'zero_wl' zero ONE non-zero low piece of the
@@ -277,22 +253,11 @@ def range_data(c, kind):
     g = torch.Generator().manual_seed(1000 + RANGE_KINDS.index(kind) + (17 if c.pass_ == 'fwd' else 0))
     w = torch.randn(K, C, Rr, S, generator=g) * 0.05
     src = torch.randn(*src_shape(c), generator=g)
-    if kind == 'wide_range':        # magnitudes over eight / twelve decades inside one tensor
-        src = src * torch.pow(10.0, torch.rand(src.shape, generator=g) * 8 - 6)
-        w = w * torch.pow(10.0, torch.rand(w.shape, generator=g) * 12 - 14)
-    elif kind == 'tiny':            # true values near 1e-34: normal fp32, but sx sits at the +100 clamp and the filter rows need 2^30
-        src, w = src * 1e-30, w * 1e-4
-    else:                           # true values near 1e20
-        src, w = src * 1e12, w * 1e8
+    # wide_range: magnitudes over eight / twelve decades inside one tensor; tiny: true values near 1e-34 -- normal fp32, but sx sits at the
+    # +100 clamp and the filter rows need 2^30; huge: true values near 1e20
+    src, w = range_scale(kind, g, src, w, (8, -6), (12, -14), (1e-30, 1e-4), (1e12, 1e8))
     f = _fwd64 if c.pass_ == 'fwd' else _dgrad64
     return src, w, f(src.double(), w.double(), None, c.geom)
-
-
-def per_row_rel(out, ref):
-    """relative L2 error of every produced channel"""
-    rows = ref.shape[1]
-    dd = (out - ref).transpose(0, 1).reshape(rows, -1).norm(dim=1)
-    return dd / ref.transpose(0, 1).reshape(rows, -1).norm(dim=1)
 
 
 # ---- the table -------------------------------------------------------------------------------------------------------------------------------
@@ -374,9 +339,6 @@ MAXPOS_N = (1, 2, 3, 4, 5, 7, 1023, 1024, 1025, 4096, 4100, 4103)
 
 
 def maxima_slots(n):
-    """where the true maximum is put in a maxima array of n slots: first, last, and from 1024 slots on the last lane of the float4 at
-    index 1023 (the end of the 4-in-flight loop of 256 threads) and the last element the float4 loops read"""
-    pos = [0, n - 1]
-    if n >= 1024:
-        pos += [p for p in (4 * 1023 + 3, 4 * (n // 4) - 1) if p < n]
-    return sorted(set(pos))
+    """split_arith.maxima_slots at NT = 256: from 1024 slots on the end of the first 4-in-flight round of 256 threads, from 4096 on the
+    second and the third load in flight"""
+    return split_arith.maxima_slots(n, NT)
