@@ -20,19 +20,17 @@ latest_net.pth (as siamese.py does), so that a run can be restated from its star
 visdom here).  One process drives one GPU.
 """
 import argparse
-import math
 import os
-import random
 import sys
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import numpy as np
 import torch
 
-from compute_inception_score import MEAN, STD      # transforms.Normalize of the reference's get_transform (classification.py:319-320)
+from pcgan_amd.util.script import (MEAN, STD, checkpoint_file, first_gpu, init_like_reference, normalized_transform, options_report,
+                                   run_epochs, seed_everything, write_report)
 
 RESNETS = ('resnet18', 'resnet34', 'resnet50')
 
@@ -91,18 +89,6 @@ def build_parser():
     return parser
 
 
-def options_report(parser, opt):
-    """the option listing printed at start and kept as <checkpoint_dir>/<name>/opt.txt, in the layout of this project's other scripts
-    (pcgan_amd/options/base_options.py): one `name: value` row per option, values that differ from the default marked"""
-    rows = ['--------------- Options -----------------']
-    for key in sorted(vars(opt)):
-        value, default = getattr(opt, key), parser.get_default(key)
-        note = '' if value == default else '\t[default: %s]' % (default,)
-        rows.append('%25s: %-30s%s' % (key, value, note))
-    rows.append('----------------- End -------------------')
-    return '\n'.join(rows)
-
-
 def get_options(argv=None, save=True):
     """parsed options plus what the rest of the script derives from them: isTrain, use_gpu, attr_bins as a list and with the open last
     bin; --weight must name every class"""
@@ -117,10 +103,7 @@ def get_options(argv=None, save=True):
     report = options_report(parser, opt)
     print(report)
     if save:
-        folder = os.path.join(opt.checkpoint_dir, opt.name)
-        os.makedirs(folder, exist_ok=True)
-        with open(os.path.join(folder, 'opt.txt'), 'w') as f:
-            f.write(report + '\n')
+        write_report(report, os.path.join(opt.checkpoint_dir, opt.name))
     return opt
 
 
@@ -150,12 +133,8 @@ class AttributeImages(torch.utils.data.Dataset):
 def get_transform(opt):
     """reference classification.py:282-321: the PIL steps of --transforms (all seven modes; the flip in train mode unless --no_flip),
     ToTensor, Normalize with the CIFAR statistics.  --use_color_jitter adds ColorJitter() with its default arguments: the identity."""
-    from pcgan_amd.data.base_dataset import TRANSFORM_MODES, pil_steps, to_tensor
-    if opt.transforms not in TRANSFORM_MODES:
-        raise ValueError('--resize_or_crop %s is not a valid option.' % opt.transforms)
-    mean = torch.tensor(MEAN, dtype=torch.float32).view(3, 1, 1)
-    std = torch.tensor(STD, dtype=torch.float32).view(3, 1, 1)
-    return lambda img: (to_tensor(pil_steps(opt, img)) - mean) / std
+    from pcgan_amd.data.base_dataset import TRANSFORM_MODES
+    return normalized_transform(opt, TRANSFORM_MODES)
 
 
 def labels_of(names, opt):
@@ -187,20 +166,6 @@ def make_loader(opt, train=True, val=False):
 
 
 # ---------------------------------------------------------------------------- model
-def init_like_reference(net):
-    """the initialisation classification.py's trainer starts from: every convolution and the fc weight ~ N(0, 0.02), every BatchNorm
-    scale ~ N(1, 0.02) with a zero shift; the fc bias keeps nn.Linear's own.  Layers are visited in registration order, so the draws
-    come out of torch's generator in the reference's order (pinned by tests/golden/classification_step.npz: <trunk>/init/*)."""
-    with torch.no_grad():
-        for m in net.modules():
-            kind = type(m).__name__
-            if 'Conv' in kind or 'Linear' in kind:
-                m.weight.normal_(0.0, 0.02)
-            elif 'BatchNorm2d' in kind:
-                m.weight.normal_(1.0, 0.02)
-                m.bias.zero_()
-
-
 def check_refusals(opt):
     """what this build does not run, raised before anything touches the device"""
     if opt.mode not in ('train', 'test'):
@@ -222,93 +187,36 @@ def get_model(opt):
     check_refusals(opt)
     net = networks.ResNet(3, opt.num_classes, opt.which_model)       # resnet101 / resnet152 raise NotImplementedError here
     if opt.mode == 'train' and not opt.continue_train:
-        init_like_reference(net)
+        init_like_reference(net, linear=True)
         if opt.pretrained_model_path:      # '' trains from the initialisation above (no ImageNet file is fetched)
             net.load_pretrained(opt.pretrained_model_path)
     else:
-        path = os.path.join(opt.checkpoint_dir, opt.name, '{}_net.pth'.format(opt.which_epoch))
-        net.load_state_dict(torch.load(path, map_location='cpu'))
+        net.load_state_dict(torch.load(checkpoint_file(opt, opt.which_epoch), map_location='cpu'))
     ops.invalidate_packed_weights()
     if opt.mode != 'train':
         net.eval()
     return net
 
 
-def device_of(opt):
-    gpu = int(opt.gpu_ids.split(',')[0]) if opt.gpu_ids else -1
-    if gpu < 0 or not torch.cuda.is_available():
-        raise RuntimeError('pcgan_amd: classification.py needs an MI355X (no CPU fallback)')
-    device = torch.device('cuda', gpu)
-    torch.cuda.set_device(device)
-    return device
-
-
-def seed_everything(seed):
-    if seed is not None:
-        random.seed(seed)
-        np.random.seed(seed)
-        torch.manual_seed(seed)
-
-
-def save(net, path):
-    torch.save({k: v.detach().cpu() for k, v in net.state_dict().items()}, path)
-
-
 # ---------------------------------------------------------------------------- train / test
 def train(opt, net, loader, loader_val=None):
     """reference classification.py:325-469"""
-    from pcgan_amd.hip.optim import FusedAdam
-    device = device_of(opt)
+    device = first_gpu(opt, 'classification.py')
     net = net.to(device)
     weight = torch.tensor(opt.weight, dtype=torch.float32, device=device) if len(opt.weight) else None      # :326-332
     save_dir = os.path.join(opt.checkpoint_dir, opt.name)
     os.makedirs(os.path.join(save_dir, 'img'), exist_ok=True)
-    optimizer = FusedAdam(net.parameters(), lr=opt.lr)         # optim.Adam(param, lr=opt.lr): betas (0.9, 0.999)
-    save(net, os.path.join(save_dir, 'init_net.pth'))
-    dataset_size = len(loader.dataset)
-    iters_per_epoch = math.ceil(dataset_size / opt.batch_size)
-    loss_history, total_iter = [], 0
-    seed_everything(opt.seed)      # the augmentation draws of the first epoch start from the seed, whatever the initialisation consumed
-    for epoch in range(opt.epoch_count, opt.num_epochs + opt.epoch_count):
-        step_losses = []                                                     # device scalars: read once, when the epoch ends
-        hits = torch.zeros((), dtype=torch.int32, device=device)
-        for img0, path0 in loader:
-            label = torch.tensor(labels_of(path0, opt), dtype=torch.int64).to(device)
-            img0 = img0.to(device)
-            total_iter += 1
-            optimizer.zero_grad()
-            loss, _, _, correct = net.classify(img0, label, weight)         # :376-380, one node: head + loss + predictions
-            loss.backward()
-            optimizer.step()
-            step_losses.append(loss.detach())
-            hits += correct
-            if total_iter % opt.print_freq == 0:
-                print('epoch %02d, iter %06d, loss: %.4f' % (epoch, total_iter, loss.item()))
-        assert len(step_losses) == iters_per_epoch
-        loss_history += torch.stack(step_losses).cpu().tolist()
-        curr_acc = {'train': int(hits) / dataset_size}                       # 1 - err_train (:426-427)
-        if loader_val is not None:
-            # as in the reference (:429-443) eval mode is NOT entered: BatchNorm normalises each validation image with its own
-            # statistics and the running statistics keep moving.  Kept on purpose; only autograd's bookkeeping is switched off.
-            hits_val = torch.zeros((), dtype=torch.int32, device=device)
-            with torch.no_grad():
-                for img0, path0 in loader_val:
-                    label = torch.tensor(labels_of(path0, opt), dtype=torch.int64).to(device)
-                    hits_val += net.classify(img0.to(device), label)[3]
-            curr_acc['val'] = int(hits_val) / len(loader_val.dataset)
-        print('epoch %02d: ' % epoch + ', '.join('%s accuracy %.4f' % kv for kv in curr_acc.items()))
-        save(net, os.path.join(save_dir, 'latest_net.pth'))
-        if epoch % opt.save_epoch_freq == 0:
-            save(net, os.path.join(save_dir, '{}_net.pth'.format(epoch)))
-    with open(os.path.join(save_dir, 'loss.txt'), 'w') as f:
-        for value in loss_history:
-            f.write(str(value) + '\n')
-    return loss_history
+
+    def forward(img, label):       # :376-380, one node: head + loss + predictions; the validation pass (:429-443) takes no class weights
+        loss, _, _, correct = net.classify(img, label, weight if torch.is_grad_enabled() else None)
+        return loss, correct
+    return run_epochs(opt, net, loader, loader_val, lambda names: torch.tensor(labels_of(names, opt), dtype=torch.int64).to(device),
+                      forward, lambda loss: loss.backward(), save_dir)
 
 
 def test(opt, net, loader):
     """reference classification.py:473-494: images in file order, one line per image, the accuracy in percent"""
-    device = device_of(opt)
+    device = first_gpu(opt, 'classification.py')
     net = net.to(device).eval()
     pred, target = [], []
     with torch.no_grad():

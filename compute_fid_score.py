@@ -49,8 +49,9 @@ def alexnet_features(weights, device):
     else:
         print('WARNING: --pretrained_model_path_IP not given: random AlexNet features')
     net.eval()
-    norm = networks.Normalize((0.4914, 0.4822, 0.4465), (0.2023, 0.1994, 0.2010))
+    from pcgan_amd.util.script import MEAN, STD
     from pcgan_amd.util.util import upsample2d
+    norm = networks.Normalize(MEAN, STD)
     return lambda batch: net(norm(upsample2d(batch.to(device) * 2 - 1, 224)))
 
 

@@ -24,8 +24,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-MEAN = (0.4914, 0.4822, 0.4465)      # transforms.Normalize of the reference's get_transform (compute_inception_score.py:74-75)
-STD = (0.2023, 0.1994, 0.2010)
+from pcgan_amd.util.script import MEAN, STD, normalized_transform      # (Normalize of the reference's get_transform, :74-75)
+
 MODES = ('resize_and_crop', 'crop', 'resize_affine_crop', 'resize_affine_center')
 RESNETS = ('resnet18', 'resnet34', 'resnet50')
 INPUT_SIZE = {'inception_v3': 299, 'resnet': 224}
@@ -106,13 +106,7 @@ def predictor(which, weights, device):
 
 def get_transform(opt):
     """the reference's transform (compute_inception_score.py:47-76): PIL image -> normalised (3, fineSize, fineSize) float32"""
-    import torch
-    from pcgan_amd.data.base_dataset import pil_steps, to_tensor
-    if opt.transforms not in MODES:
-        raise ValueError('--resize_or_crop %s is not a valid option.' % opt.transforms)
-    mean = torch.tensor(MEAN, dtype=torch.float32).view(3, 1, 1)
-    std = torch.tensor(STD, dtype=torch.float32).view(3, 1, 1)
-    return lambda img: (to_tensor(pil_steps(opt, img)) - mean) / std
+    return normalized_transform(opt, MODES)
 
 
 def image_paths(opt):

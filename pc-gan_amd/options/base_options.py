@@ -15,6 +15,7 @@ import torch
 from .. import models
 from .. import data
 from ..util import util
+from ..util.script import options_report, seed_everything
 
 _INF = float('inf')
 
@@ -96,13 +97,7 @@ class BaseOptions():
         return parser.parse_args()
 
     def print_options(self, opt):
-        lines = ['----------------- Options ---------------']
-        for k, v in sorted(vars(opt).items()):
-            default = self.parser.get_default(k)
-            comment = '\t[default: %s]' % str(default) if v != default else ''
-            lines.append('{:>25}: {:<30}{}'.format(str(k), str(v), comment))
-        lines.append('----------------- End -------------------')
-        message = '\n'.join(lines)
+        message = options_report(self.parser, opt, '----------------- Options ---------------')
         print(message)
         if int(os.environ.get('RANK', '0')) != 0:
             return
@@ -133,11 +128,6 @@ class BaseOptions():
         if len(opt.gpu_ids) > 0:
             torch.cuda.set_device(opt.gpu_ids[0])
         opt.attr_bins = util.str2list(opt.attr_bins)
-        if opt.seed is not None:
-            import numpy as np
-            import random
-            random.seed(opt.seed)
-            np.random.seed(opt.seed)
-            torch.manual_seed(opt.seed)
+        seed_everything(opt.seed)
         self.opt = opt
         return self.opt

@@ -15,13 +15,12 @@ BatchNorm, then pooling + MSELoss + the "within --delta" count + the loss gradie
 passes and one fused Adam launch.  The loss is read on the host where the reference prints it (--print_freq) and once per epoch for
 loss.txt; the hit count stays on the device until the epoch ends.
 
-Dataset, loader, transforms, device and checkpoint helpers are classification.py's.  Build-only flag: --seed (random / numpy / torch;
+Dataset, loader and transforms are classification.py's, the epoch loop is shared with it (util/script.py).  Build-only flag: --seed (random / numpy / torch;
 the reference sets none).  Build-only artefact: --mode train also writes init_net.pth, the weights before the first iteration.
 loss.txt has one line per iteration (the reference appends only at --print_freq).  The validation loader takes single images, as
 classification.py's.  --display_id is accepted and plots nothing (no visdom here).  One process drives one GPU.
 """
 import argparse
-import math
 import os
 import sys
 
@@ -32,9 +31,12 @@ if ROOT not in sys.path:
 import numpy as np
 import torch
 
-import classification as K      # the dataset and loader, transforms, init_like_reference, device_of, save, seed_everything, the report
+import classification as K      # the dataset and loader, transforms
+from pcgan_amd.util.script import checkpoint_file, first_gpu, init_like_reference, options_report, run_epochs, write_report
+from pcgan_amd.util.util import get_attr_value as get_attr      # reference regression.py:182-183
 
 BASES = ('alexnet', 'resnet18', 'resnet34', 'resnet50')
+SCRIPT = 'classification.py'      # the name in the "needs an MI355X" error, unchanged since the device helper was classification.py's
 
 
 # ---------------------------------------------------------------------------- options
@@ -98,24 +100,16 @@ def get_options(argv=None, save=True):
     opt.isTrain = opt.mode == 'train'
     opt.use_gpu = bool(opt.gpu_ids) and torch.cuda.is_available()
     opt.test_batch_size = 1
-    report = K.options_report(parser, opt)
+    report = options_report(parser, opt)
     print(report)
     if save:
-        folder = os.path.join(opt.checkpoint_dir, opt.name)
-        os.makedirs(folder, exist_ok=True)
-        with open(os.path.join(folder, 'opt.txt'), 'w') as f:
-            f.write(report + '\n')
+        write_report(report, os.path.join(opt.checkpoint_dir, opt.name))
     mean, std = opt.embedding_mean, opt.embedding_std
     opt.embedding_normalize = lambda x: (x - mean) / std
     return opt
 
 
 # ---------------------------------------------------------------------------- labels
-def get_attr(fname):
-    """reference regression.py:182-183"""
-    return float(fname.split('_')[0])
-
-
 def labels_of(names, opt, feature_dim):
     """the fp32 (B, feature_dim, 1, 1) label tensor of a batch of file names (regression.py:346-350): the float each name starts with,
     normalised by --embedding_mean / --embedding_std.  As in the reference the view only fits feature_dim = 1."""
@@ -147,12 +141,11 @@ def get_model(opt):
     net = networks.RegressionNetwork(base, pooling=opt.pooling, cnn_dim=opt.cnn_dim, cnn_pad=opt.cnn_pad,
                                      cnn_relu_slope=opt.cnn_relu_slope)
     if opt.mode == 'train':
-        K.init_like_reference(net)
+        init_like_reference(net, linear=True)
         if opt.pretrained_model_path:      # '' trains from the initialisation above (no ImageNet file is fetched)
             net.load_pretrained(opt.pretrained_model_path)
     else:
-        path = os.path.join(opt.checkpoint_dir, opt.name, '{}_net.pth'.format(opt.which_epoch))
-        net.load_state_dict(torch.load(path, map_location='cpu'), strict=False)        # "HACK: strict=False" (:268-269)
+        net.load_state_dict(torch.load(checkpoint_file(opt, opt.which_epoch), map_location='cpu'), strict=False)   # "HACK" (:268-269)
         net.eval()
     ops.invalidate_packed_weights()
     return net
@@ -162,57 +155,22 @@ def get_model(opt):
 def train(opt, net, loader, loader_val=None):
     """reference regression.py:320-428"""
     from pcgan_amd.hip import functional as HF
-    from pcgan_amd.hip.optim import FusedAdam
-    device = K.device_of(opt)
+    device = first_gpu(opt, SCRIPT)
     net = net.to(device)
     save_dir = os.path.join(opt.checkpoint_dir, opt.name)
     os.makedirs(save_dir, exist_ok=True)
-    optimizer = FusedAdam(net.parameters(), lr=opt.lr)         # optim.Adam(net.parameters(), lr=opt.lr): betas (0.9, 0.999)
-    K.save(net, os.path.join(save_dir, 'init_net.pth'))
-    dataset_size = len(loader.dataset)
-    iters_per_epoch = math.ceil(dataset_size / opt.batch_size)
-    loss_history, total_iter = [], 0
-    K.seed_everything(opt.seed)    # the augmentation draws of the first epoch start from the seed, whatever the initialisation consumed
-    for epoch in range(opt.epoch_count, opt.num_epochs + opt.epoch_count):
-        step_losses = []                                                     # device scalars: read once, when the epoch ends
-        hits = torch.zeros((), dtype=torch.int32, device=device)
-        for img0, path0 in loader:
-            label = labels_of(path0, opt, net.feature_dim).to(device)
-            img0 = img0.to(device)
-            total_iter += 1
-            optimizer.zero_grad()
-            loss, _, within = net.regress(img0, label, opt.delta)           # :359-363, one node: pooling + loss + accuracy
-            loss.backward(HF.unit_gradient(loss))                            # the gradient the forward launch wrote, handed on as it is
-            optimizer.step()
-            step_losses.append(loss.detach())
-            hits += within
-            if total_iter % opt.print_freq == 0:
-                print('epoch %02d, iter %06d, loss: %.4f' % (epoch, total_iter, loss.item()))
-        assert len(step_losses) == iters_per_epoch
-        loss_history += torch.stack(step_losses).cpu().tolist()
-        curr_acc = {'train': int(hits) / dataset_size}                       # :385
-        if loader_val is not None:
-            # as in the reference (:388-402) eval mode is NOT entered: BatchNorm normalises each validation batch with its own
-            # statistics and the running statistics keep moving.  Kept on purpose; only autograd's bookkeeping is switched off.
-            hits_val = torch.zeros((), dtype=torch.int32, device=device)
-            with torch.no_grad():
-                for img0, path0 in loader_val:
-                    label = labels_of(path0, opt, net.feature_dim).to(device)
-                    hits_val += net.regress(img0.to(device), label, opt.delta)[2]
-            curr_acc['val'] = int(hits_val) / len(loader_val.dataset)
-        print('epoch %02d: ' % epoch + ', '.join('%s accuracy %.4f' % kv for kv in curr_acc.items()))
-        K.save(net, os.path.join(save_dir, 'latest_net.pth'))
-        if epoch % opt.save_epoch_freq == 0:
-            K.save(net, os.path.join(save_dir, '{}_net.pth'.format(epoch)))
-    with open(os.path.join(save_dir, 'loss.txt'), 'w') as f:
-        for value in loss_history:
-            f.write(str(value) + '\n')
-    return loss_history
+
+    def forward(img, label):       # :359-363, one node: pooling + loss + accuracy
+        loss, _, within = net.regress(img, label, opt.delta)
+        return loss, within
+    # backward: the gradient the forward launch wrote, handed on as it is
+    return run_epochs(opt, net, loader, loader_val, lambda names: labels_of(names, opt, net.feature_dim).to(device),
+                      forward, lambda loss: loss.backward(HF.unit_gradient(loss)), save_dir)
 
 
 def embedding(opt, net, loader):
     """reference regression.py:432-448: images in file order, one per pass, in eval mode"""
-    device = K.device_of(opt)
+    device = first_gpu(opt, SCRIPT)
     net = net.to(device).eval()
     features, labels = [], []
     with torch.no_grad():

@@ -33,6 +33,7 @@ from pcgan_amd.data.base_dataset import decode_raw, get_transform
 from pcgan_amd.hip import parallel
 from pcgan_amd.hip.optim import FusedAdam
 from pcgan_amd.models import networks
+from pcgan_amd.util.script import checkpoint_file, first_gpu, init_like_reference, save_state
 from pcgan_amd.util.util import reparameterize, str2bool
 
 
@@ -173,17 +174,6 @@ def pair_batch(batch, tf, device, rank=0, world=1):
     return tf(raw0, aug0), tf(raw1, aug1), label.to(device)
 
 
-def init_like_reference(net):
-    """weights_init of the reference (siamese.py:288-296): every conv N(0, 0.02), BatchNorm weight N(1, 0.02), bias 0"""
-    for m in net.modules():
-        kind = m.__class__.__name__
-        if 'Conv' in kind:
-            m.weight.data.normal_(0.0, 0.02)
-        elif 'BatchNorm2d' in kind:
-            m.weight.data.normal_(1.0, 0.02)
-            m.bias.data.fill_(0)
-
-
 def build_net(opt, device):
     if 'resnet' not in opt.which_model:
         raise NotImplementedError('pcgan_amd: rating trunk [%s] is outside the MI355X hot path' % opt.which_model)
@@ -193,11 +183,10 @@ def build_net(opt, device):
     net = networks.SiameseNetwork(base, pooling=opt.pooling, cnn_dim=[] if opt.no_cnn else opt.cnn_dim, cnn_pad=opt.cnn_pad,
                                   cnn_relu_slope=opt.cnn_relu_slope, fc_dim=opt.fc_dim, use_cxn=opt.use_cxn, noisy=opt.noisy,
                                   drop_layer=networks.get_dropout_layer(dropout=opt.bnn_dropout), rsample=opt.rsample)
-    save_dir = os.path.join(opt.checkpoint_dir, opt.name)
     if opt.continue_train:
-        net.load_state_dict(torch.load(os.path.join(save_dir, '%s_net.pth' % opt.which_epoch), map_location='cpu'), strict=False)
+        net.load_state_dict(torch.load(checkpoint_file(opt, opt.which_epoch), map_location='cpu'), strict=False)
     else:
-        init_like_reference(net)
+        init_like_reference(net, linear=False)      # weights_init of the reference (siamese.py:288-296) leaves Linear layers alone
         if opt.pretrained_model_path:
             net.load_pretrained(opt.pretrained_model_path)
     return net.to(device)
@@ -258,19 +247,10 @@ def predictions(prob, draw_thresh):
     return torch.where(draw, torch.ones_like(p), torch.where(p > 0.5, torch.full_like(p, 2.0), torch.zeros_like(p))).long()
 
 
-def save(net, path):
-    if not parallel.is_distributed() or torch.distributed.get_rank() == 0:
-        torch.save({k: v.detach().cpu() for k, v in net.state_dict().items()}, path)
-
-
 def train(opt):
     world, rank, local = parallel.init_process_group()
     torch.manual_seed(opt.seed)
-    gpu = int(opt.gpu_ids.split(',')[0])
-    if gpu < 0 or not torch.cuda.is_available():
-        raise RuntimeError('pcgan_amd: siamese.py needs an MI355X (no CPU fallback)')
-    device = torch.device('cuda', local % torch.cuda.device_count() if world > 1 else gpu)
-    torch.cuda.set_device(device)
+    device = first_gpu(opt, 'siamese.py', local % max(1, torch.cuda.device_count()) if world > 1 else None)      # one process per GPU
     net = build_net(opt, device)
     parallel.broadcast_parameters(net)
     criterion = networks.BinaryNLLLoss()
@@ -285,7 +265,7 @@ def train(opt):
     loader = make_loader(opt, data, tf, batch_size=opt.batch_size, shuffle=not opt.serial_batches)
     save_dir = os.path.join(opt.checkpoint_dir, opt.name)
     os.makedirs(save_dir, exist_ok=True)
-    save(net, os.path.join(save_dir, 'init_net.pth'))
+    save_state(net, checkpoint_file(opt, 'init'))
     history, total = [], 0
     for epoch in range(opt.epoch_count, opt.num_epochs + opt.epoch_count):
         wrong = seen = 0
@@ -310,7 +290,7 @@ def train(opt):
                 if rank == 0:
                     print('epoch %02d, iter %06d, loss: %.4f' % (epoch, total, value))
             if total % opt.save_latest_freq == 0:
-                save(net, os.path.join(save_dir, 'latest_net.pth'))
+                save_state(net, checkpoint_file(opt, 'latest'))
         if rank == 0:
             print('epoch %02d: train accuracy %.4f' % (epoch, 1.0 - wrong / max(seen, 1)))
         if scheduler_sigma is not None:
@@ -318,9 +298,9 @@ def train(opt):
             if rank == 0:
                 print('--->> lr      : %g' % optimizer.param_groups[0]['lr'])
                 print('--->> lr_sigma: %g' % optimizer_sigma.param_groups[0]['lr'])
-        save(net, os.path.join(save_dir, 'latest_net.pth'))
+        save_state(net, checkpoint_file(opt, 'latest'))
         if epoch % opt.save_epoch_freq == 0:
-            save(net, os.path.join(save_dir, '%d_net.pth' % epoch))
+            save_state(net, checkpoint_file(opt, epoch))
     if rank == 0:
         with open(os.path.join(save_dir, 'loss.txt'), 'w') as f:
             f.writelines('%r\n' % v for v in history)
@@ -367,15 +347,6 @@ def get_attr_value(fname):
     return float(fname.split()[1]) if len(fname.split()) > 1 else float(fname.split('_')[0])
 
 
-def _device(opt):
-    gpu = int(opt.gpu_ids.split(',')[0])
-    if gpu < 0 or not torch.cuda.is_available():
-        raise RuntimeError('pcgan_amd: siamese.py needs an MI355X (no CPU fallback)')
-    device = torch.device('cuda', gpu)
-    torch.cuda.set_device(device)
-    return device
-
-
 def build_feature_net(opt, device, state_dict=None):
     """the single-image rating net of `--mode embedding` (reference get_model, siamese.py:450-476): SiameseFeature loaded from
     <checkpoint_dir>/<name>/<which_epoch>_net.pth with strict=False (the trainer's comparison head `cxn` / `fc` is not part of it),
@@ -388,7 +359,7 @@ def build_feature_net(opt, device, state_dict=None):
                                   cnn_relu_slope=opt.cnn_relu_slope, noisy=opt.noisy,
                                   drop_layer=networks.get_dropout_layer(dropout=opt.bnn_dropout))
     if state_dict is None:
-        state_dict = torch.load(os.path.join(opt.checkpoint_dir, opt.name, '%s_net.pth' % opt.which_epoch), map_location='cpu')
+        state_dict = torch.load(checkpoint_file(opt, opt.which_epoch), map_location='cpu')
     net.load_state_dict(state_dict, strict=False)
     for p in net.parameters():
         p.requires_grad = False
@@ -400,7 +371,7 @@ def embedding(opt, net=None, which_epoch=None):
     as features_<epoch>.npy / labels_<epoch>.npy (+ stds_ with --noisy: exp(logvar / 2); + vars_ with --bayesian: the variance over
     --T MC-dropout passes, the feature being their mean) under <checkpoint_dir>/<name>/ -- the ratings from which the GAN's
     --embedding_mean / --embedding_std / --embedding_bins are derived.  Returns (features, labels)."""
-    device = _device(opt)
+    device = first_gpu(opt, 'siamese.py')
     opt.isTrain = False if opt.no_flip else True      # (get_transform flips only in train mode; the reference passes its own opt)
     if net is None:
         net = build_feature_net(opt, device)
@@ -458,7 +429,7 @@ def test(opt):
     over --datafile.  The reference builds a SiameseFeature for this mode and then calls it on pairs (get_model, :450), which cannot
     run; what its `test` evidently means -- the trained SiameseNetwork's P(first > second) against the labels with the draw band
     --draw_prob_thresh -- is what runs here.  Returns the accuracy in percent."""
-    device = _device(opt)
+    device = first_gpu(opt, 'siamese.py')
     opt.continue_train = True                  # build_net then loads <which_epoch>_net.pth
     net = build_net(opt, device)
     data = PairDataset(opt, opt.dataroot, opt.datafile)
@@ -505,7 +476,7 @@ def attention(opt):
       * no visdom window, no time.sleep(1), no debugging prints; the guided-ReLU variant (update_relus) is out of scope."""
     from pcgan_amd.hip import functional as HF, ops
     from pcgan_amd.util.gradcam import GradCAM
-    device = _device(opt)
+    device = first_gpu(opt, 'siamese.py')
     opt.continue_train = True                  # build_net then loads <which_epoch>_net.pth
     net = build_net(opt, device)
     data = PairDataset(opt, opt.dataroot, opt.datafile)

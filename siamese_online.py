@@ -37,6 +37,7 @@ import torch
 import siamese as S
 from pcgan_amd.hip import parallel
 from pcgan_amd.hip.optim import FusedAdam
+from pcgan_amd.util.script import checkpoint_file, first_gpu, options_report, save_state, write_report
 
 SELECTORS = {'hard': False, 'easy': True}       # -> descending: hard keeps the SMALLEST squared distances (:227-228)
 
@@ -130,21 +131,6 @@ def check_options(opt):
                                   'batch that is sharded between processes')
 
 
-def print_options(opt, parser):
-    """the reference's option dump (:105-124), printed and written to <checkpoint_dir>/<name>/opt.txt"""
-    message = '--------------- Options -----------------\n'
-    for k, v in sorted(vars(opt).items()):
-        default = parser.get_default(k)
-        comment = '\t[default: %s]' % str(default) if v != default else ''
-        message += '{:>25}: {:<30}{}\n'.format(str(k), str(v), comment)
-    message += '----------------- End -------------------'
-    print(message)
-    expr_dir = os.path.join(opt.checkpoint_dir, opt.name)
-    os.makedirs(expr_dir, exist_ok=True)
-    with open(os.path.join(expr_dir, 'opt.txt'), 'wt') as f:
-        f.write(message + '\n')
-
-
 def get_options(argv=None, save=True):
     """reference Options.get_options (:84-103); save=False neither removes online.txt nor writes opt.txt"""
     parser = build_parser()
@@ -162,7 +148,9 @@ def get_options(argv=None, save=True):
         online = os.path.join(opt.checkpoint_dir, opt.name, 'online.txt')
         if os.path.exists(online):
             os.remove(online)
-        print_options(opt, parser)
+        report = options_report(parser, opt)       # the reference's option dump (:105-124), printed and kept as opt.txt
+        print(report)
+        write_report(report, os.path.join(opt.checkpoint_dir, opt.name))
     return opt
 
 
@@ -261,7 +249,7 @@ def build_optimizer(opt, net):
 
 def train(opt):
     torch.manual_seed(opt.seed)
-    device = S._device(opt)
+    device = first_gpu(opt, 'siamese.py')      # (the error names the script whose device helper this was)
     net = S.build_net(opt, device)
     optimizer = build_optimizer(opt, net)
     data = OnlinePairDataset(opt, opt.dataroot, opt.datafile)
@@ -285,9 +273,9 @@ def train(opt):
                 history.append(value)
                 print('epoch %02d, iter %06d, loss: %.4f' % (epoch, total_iter, value))
             if total_iter % opt.save_latest_freq == 0:
-                S.save(net, os.path.join(save_dir, 'latest_net.pth'))
+                save_state(net, checkpoint_file(opt, 'latest'))
                 if epoch % opt.save_epoch_freq == 0:
-                    S.save(net, os.path.join(save_dir, '%d_net.pth' % epoch))
+                    save_state(net, checkpoint_file(opt, epoch))
         print('epoch %02d: train accuracy %.4f' % (epoch, 1.0 - log.wrong / len(data)))
     with open(os.path.join(save_dir, 'loss.txt'), 'w') as f:
         f.writelines('%r\n' % v for v in history)
@@ -297,7 +285,7 @@ def train(opt):
 
 
 def embedding(opt):
-    device = S._device(opt)
+    device = first_gpu(opt, 'siamese.py')      # (the error names the script whose device helper this was)
     net = S.build_feature_net(opt, device).eval()
     return S.embedding(opt, net=net)
 
