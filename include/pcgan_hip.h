@@ -799,7 +799,7 @@ int pcgan_timer_read(int kind, float* ms, int cap);
  * reflection padding, 2 data gradient, 3 data gradient gathering reflection mirrors), BM, BP, K split, phases}; entries past
  * PCGAN_IGEMM_LAUNCH_INFO are 0.  PCGAN_IGEMM_SMALLM has no tile: there BM names the kernel (1 strip, 2 few taps, 3 generic), BP the strip
  * kernel's instantiation as NR * 10 + MO (43, 44, 73, 74; 0 for the other two) and the K split is the strip kernel's channel split.
- * The window / split / thin kernels do not record. */
+ * The thin kernels do not record; the bsplit entries (per-tap and window kernel) have a record of their own, pcgan_bsplit_last_launch. */
 #define PCGAN_IGEMM_LAUNCH_INFO 7
 #define PCGAN_IGEMM_HGEMM_F16X2 1  /* hgemm_kernel, fp32 tensors as two scaled fp16 pieces */
 #define PCGAN_IGEMM_HGEMM_BF16 2   /* hgemm_kernel, bf16 tensors, one product */
@@ -813,7 +813,7 @@ int pcgan_igemm_last_launch(int* info, int n);
  * (+1 per recorded launch), family (PCGAN_WGRAD_*), padding mode (0 zero, 1 reflection), BM (0 for the small-M kernels), VECA (dY fetched
  * four pixels at a time; tile kernels only), variant (see the families), storage type (PCGAN_F32 / PCGAN_BF16), splits, units per split
  * (chunks of 32 pixels; strips for PCGAN_WGRAD_STRIP)}; entries past PCGAN_WGRAD_LAUNCH_INFO are 0.  The per-tap (hsplit) weight gradient
- * has a record of its own (pcgan_hwgrad_last_launch below); the bsplit / row-ring / direct weight gradients do not record. */
+ * has a record of its own (pcgan_hwgrad_last_launch below), the bsplit weight gradient too (pcgan_bsplit_last_launch); the row-ring / direct forms do not record. */
 #define PCGAN_WGRAD_LAUNCH_INFO 9
 #define PCGAN_WGRAD_TILE2 1   /* wgrad2_kernel (tap-aligned K tiles, pipelined); variant = taps per K tile, 2 | 1 */
 #define PCGAN_WGRAD_TILE 2    /* wgrad_kernel; variant = KMODE 0 (generic) | 1 (per-thread tap) | 2 (one tap per K tile) */
@@ -830,6 +830,17 @@ int pcgan_wgrad_last_launch(int* info, int n);
  * entries past PCGAN_HWGRAD_LAUNCH_INFO are 0. */
 #define PCGAN_HWGRAD_LAUNCH_INFO 12
 int pcgan_hwgrad_last_launch(int* info, int n);
+/* Launch record of the bsplit entries (host memory, no synchronisation, a record of its own): written by pcgan_conv2d_fwd_bsplit,
+ * pcgan_conv2d_bwd_data_bsplit and pcgan_conv2d_bwd_weight_bsplit when they issue the launch of their main kernel (an attempted launch:
+ * the record is written before the launch status is read).  info[0 .. n) = {sequence number (+1 per recorded launch), kernel (0 the
+ * per-tap kernel bsplit_conv_fwd_kernel, 1 the window kernel bsplit_halo_kernel), mode (per-tap: 0 forward zero padding, 1 forward
+ * reflection padding, 2 data gradient, 3 weight gradient; window: 0 forward, 1 data gradient), BM (128 | 256), storage type (PCGAN_F32 /
+ * PCGAN_BF16), row tiles, pixel tiles of 128 pixels (weight gradient: column tiles of 128 columns (c, r, s); data gradient of the per-tap
+ * kernel: the tiles of its three row classes together), stages in all, splits of the reduction (1 outside the weight gradient), stages
+ * per split, padded copy of the weight gradient (0 none, 1 element-per-thread kernel, 2 wave-per-plane kernel)}; entries past
+ * PCGAN_BSPLIT_LAUNCH_INFO are 0. */
+#define PCGAN_BSPLIT_LAUNCH_INFO 11
+int pcgan_bsplit_last_launch(int* info, int n);
 
 #ifdef __cplusplus
 }

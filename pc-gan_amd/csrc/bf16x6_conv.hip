@@ -107,6 +107,22 @@ static BsplitArgs bsplit_args(const pcgan_conv_desc* d, int pass, const PackGeom
     return a;
 }
 
+// host-side record of the last launch the bsplit entries issued (pcgan_bsplit_last_launch): a record of its own, written by the forward,
+// the data gradient and the weight gradient once their main kernel's launch has been attempted, before its status is read
+static std::mutex g_bsplit_mu;
+static int g_bsplit_rec[PCGAN_BSPLIT_LAUNCH_INFO] = {0};
+static void bsplit_record(int kernel, int mode, int bm, int dtype, int row_tiles, long tiles, int nst, int splits, int nst_split, int copy) {
+    std::lock_guard<std::mutex> lk(g_bsplit_mu);
+    const int v[PCGAN_BSPLIT_LAUNCH_INFO] = {g_bsplit_rec[0] + 1, kernel, mode, bm, dtype, row_tiles, (int)tiles, nst, splits, nst_split, copy};
+    for (int i = 0; i < PCGAN_BSPLIT_LAUNCH_INFO; ++i) g_bsplit_rec[i] = v[i];
+}
+// the window kernel's launch in the same terms: one 256-row tile form, pixel tiles of 128 pixels, stages = (16-channel chunk, tap)
+static int launch_halo_recorded(int mode, const pcgan_conv_desc* d, const HaloArgs& h, hipStream_t st) {
+    const int e = launch_halo(mode, bsplit_pk(d), d->W, h, st);
+    bsplit_record(1, mode, 256, d->dtype, h.nMt, (long)d->N * d->H * d->W / 128, h.nch * 9, 1, h.nch * 9, 0);
+    return e;
+}
+
 }  // namespace pcgan
 
 using namespace pcgan;
@@ -132,10 +148,13 @@ extern "C" int pcgan_conv2d_fwd_bsplit(const pcgan_conv_desc* d, const void* x, 
     const PackGeom g = bsplit_geom(d, PCGAN_PASS_FWD);
     PCGAN_CHECK(g.bytes < 0x80000000ull, "conv2d_fwd_bsplit: packed weights beyond 2 GiB");
     if (d->pad_mode == 1 && d->R == 3 && d->S == 3 && d->pad == 1 && halo_shape(d->C, d->K, d->H, d->W))
-        return launch_halo(BH_FWD, bsplit_pk(d), d->W, halo_args(d, PCGAN_PASS_FWD, x, packed, g.bytes, bias, y, act, slope), (hipStream_t)s);
+        return launch_halo_recorded(BH_FWD, d, halo_args(d, PCGAN_PASS_FWD, x, packed, g.bytes, bias, y, act, slope), (hipStream_t)s);
     const long ptiles = ((long)d->N * d->P * d->Q + 127) / 128;
-    return launch_bsplit(d->pad_mode == 1 ? BS_FWD_REFLECT : BS_FWD_ZERO, d->dtype, g.bm, dim3((unsigned)(ptiles * g.nMt)),
-                         bsplit_args(d, PCGAN_PASS_FWD, g, x, packed, bias, y, act, slope), (hipStream_t)s);
+    const int mode = d->pad_mode == 1 ? BS_FWD_REFLECT : BS_FWD_ZERO;
+    const int e = launch_bsplit(mode, d->dtype, g.bm, dim3((unsigned)(ptiles * g.nMt)), bsplit_args(d, PCGAN_PASS_FWD, g, x, packed, bias, y, act, slope),
+                                (hipStream_t)s);
+    bsplit_record(0, mode, g.bm, d->dtype, g.nMt, ptiles, g.nst, 1, g.nst, 0);
+    return e;
 }
 
 // ---- data gradient of the reflection-padded 3x3 stride-1 convolution ---------------------------------------------------------
@@ -163,8 +182,8 @@ extern "C" int pcgan_conv2d_bwd_data_bsplit(const pcgan_conv_desc* d, const void
     const PackGeom g = bsplit_geom(d, PCGAN_PASS_BWD_DATA);      // one row class
     PCGAN_CHECK(3 * g.bytes < 0x80000000ull, "conv2d_bwd_data_bsplit: packed weights beyond 2 GiB");
     if (halo_shape(d->K, d->C, d->H, d->W))      // plain flipped weights = row class 0 of the packed buffer
-        return launch_halo(BH_DGRAD, bsplit_pk(d), d->W, halo_args(d, PCGAN_PASS_BWD_DATA, dy, packed, g.bytes, nullptr, dx, PCGAN_ACT_NONE, 0.f),
-                           (hipStream_t)s);
+        return launch_halo_recorded(BH_DGRAD, d, halo_args(d, PCGAN_PASS_BWD_DATA, dy, packed, g.bytes, nullptr, dx, PCGAN_ACT_NONE, 0.f),
+                                    (hipStream_t)s);
     BsplitArgs a = bsplit_args(d, PCGAN_PASS_BWD_DATA, g, dy, packed, nullptr, dx, PCGAN_ACT_NONE, 0.f);
     a.phase_bytes = (unsigned)g.bytes;
     a.a_bytes = (unsigned)(3 * g.bytes);
@@ -175,12 +194,15 @@ extern "C" int pcgan_conv2d_bwd_data_bsplit(const pcgan_conv_desc* d, const void
         t += ((long)d->N * rows[p] * d->W + 127) / 128;
     }
     a.tstart[3] = (int)t;
-    return launch_bsplit(BS_DGRAD_REFLECT, d->dtype, g.bm, dim3((unsigned)(t * a.nMt)), a, (hipStream_t)s);
+    const int e = launch_bsplit(BS_DGRAD_REFLECT, d->dtype, g.bm, dim3((unsigned)(t * a.nMt)), a, (hipStream_t)s);
+    bsplit_record(0, BS_DGRAD_REFLECT, g.bm, d->dtype, g.nMt, t, g.nst, 1, g.nst, 0);
+    return e;
 }
 
 // ---- weight gradient ------------------------------------------------------------------------------------------------------
 extern "C" int pcgan_conv2d_bsplit_wgrad_supported(const pcgan_conv_desc* d) {
-    return d && d->stride == 1 && d->pad_mode == 1 && d->R == 3 && d->S == 3 && d->pad == 1 && d->W % 16 == 0 && d->K >= 32 &&
+    return d && d->stride == 1 && d->pad_mode == 1 && d->R == 3 && d->S == 3 && d->pad == 1 && d->W % 16 == 0 &&
+           (d->K == 128 || d->K == 256) &&      // one full row tile: all pcgan_conv2d_bwd_weight_bsplit builds
            d->P == d->H && d->Q == d->W && (size_t)d->N * d->C * (d->H + 2) * (d->W + 2) * 4 < 0x80000000ull &&
            (size_t)d->N * d->H * d->W * 3 * 2 * (size_t)bsplit_bm(d->K) < 0x80000000ull;
 }
@@ -242,7 +264,9 @@ extern "C" int pcgan_conv2d_bwd_weight_bsplit(const pcgan_conv_desc* d, const vo
     a.nst_split = w.nst_split;
     a.x_bytes = (unsigned)((size_t)d->N * d->C * (d->H + 2) * (d->W + 2) * es_of(d));
     const dim3 grid((unsigned)(((d->C * 9 + 127) / 128) * w.nMt), (unsigned)w.splits);
-    if (int e = launch_bsplit(BS_WGRAD, d->dtype, w.bm, grid, a, st)) return e;
+    const int e = launch_bsplit(BS_WGRAD, d->dtype, w.bm, grid, a, st);
+    bsplit_record(0, BS_WGRAD, w.bm, d->dtype, w.nMt, (d->C * 9 + 127) / 128, w.nst, w.splits, w.nst_split, pad_copy_form(d->N * d->C, d->H, d->W, 1));
+    if (e) return e;
     return launch_wgrad_reduce(part, dw, w.splits, (size_t)d->K * d->C * 9, accumulate, st);
 }
 
@@ -458,6 +482,14 @@ extern "C" int pcgan_conv2d_bwd_weight_hsplit(const pcgan_conv_desc* d, const vo
     }
     if (e) return e;
     return launch_wgrad_reduce(part, dw, w.splits, (size_t)d->K * d->C * d->R * d->S, accumulate, st);
+}
+
+extern "C" int pcgan_bsplit_last_launch(int* info, int n) {
+    using namespace pcgan;
+    PCGAN_CHECK(info != nullptr && n > 0, "bsplit_last_launch: null output");
+    std::lock_guard<std::mutex> lk(g_bsplit_mu);
+    for (int i = 0; i < n; ++i) info[i] = i < PCGAN_BSPLIT_LAUNCH_INFO ? g_bsplit_rec[i] : 0;
+    return 0;
 }
 
 extern "C" int pcgan_hwgrad_last_launch(int* info, int n) {

@@ -147,6 +147,7 @@ SIGNATURES = {
     'pcgan_igemm_last_launch': (_i, [ctypes.POINTER(_i), _i]),
     'pcgan_wgrad_last_launch': (_i, [ctypes.POINTER(_i), _i]),
     'pcgan_hwgrad_last_launch': (_i, [ctypes.POINTER(_i), _i]),
+    'pcgan_bsplit_last_launch': (_i, [ctypes.POINTER(_i), _i]),
     'pcgan_conv2d_hgemm_supported': (_i, [_dp, _i]),
     'pcgan_conv2d_hgemm_pack': (_i, [_dp, _i, _vp, _vp, _vp, _vp]),
     'pcgan_conv2d_fwd_packed_hsplit': (_i, [_dp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _sz, _vp]),

@@ -670,7 +670,7 @@ def _wgrad_on_matrix_pipe(c):
 
 _WGRAD_ROUTES = (
     _Route('hsplit', None, _wgrad_on_matrix_pipe, lambda c: int(c.lib.pcgan_conv2d_hsplit_wgrad_workspace_bytes(c.dref)), True, _wgrad_hsplit),
-    _Route('bsplit', None, lambda c: c.split and c.K in (128, 256) and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS and c.lib.pcgan_conv2d_bsplit_wgrad_supported(c.dref),
+    _Route('bsplit', None, lambda c: c.split and c.N * c.H * c.W >= BSPLIT_MIN_PIXELS and c.lib.pcgan_conv2d_bsplit_wgrad_supported(c.dref),      # (K = 128 | 256)
            lambda c: int(c.lib.pcgan_conv2d_bsplit_wgrad_workspace_bytes(c.dref)), False, _wgrad_bsplit),
     _Route('generic', None, lambda c: True, _ws_generic(_L.PASS_BWD_WEIGHT), False, _wgrad_generic),      # fp32-MFMA / small-M weight-gradient kernels
 )
@@ -1014,6 +1014,19 @@ def hwgrad_last_launch():
     buf = (ctypes.c_int * len(HWGRAD_FIELDS))()
     _L.check(_L.load().pcgan_hwgrad_last_launch(buf, len(HWGRAD_FIELDS)), 'hwgrad_last_launch')
     return dict(zip(HWGRAD_FIELDS, list(buf)))
+
+
+BSPLIT_FIELDS = ('seq', 'kernel', 'mode', 'bm', 'dtype', 'row_tiles', 'tiles', 'stages', 'splits', 'stages_per_split', 'copy')
+
+
+def bsplit_last_launch():
+    """what the last launch of the bsplit entries was (pcgan_bsplit_last_launch, host memory): BSPLIT_FIELDS -> int; kernel 0 = the
+    per-tap kernel (mode 0 forward zero padding, 1 forward reflection padding, 2 data gradient, 3 weight gradient), 1 = the window kernel
+    (mode 0 forward, 1 data gradient); tiles = pixel tiles, column tiles in the weight gradient; copy = the weight gradient's padded copy
+    (1 element kernel, 2 wave per plane); seq grows by one per recorded launch"""
+    buf = (ctypes.c_int * len(BSPLIT_FIELDS))()
+    _L.check(_L.load().pcgan_bsplit_last_launch(buf, len(BSPLIT_FIELDS)), 'bsplit_last_launch')
+    return dict(zip(BSPLIT_FIELDS, list(buf)))
 
 
 # ---------------------------------------------------------------- pointwise

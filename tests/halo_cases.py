@@ -143,6 +143,39 @@ def fold_mask(fold, H, W):
 
 
 # ---- data, reference, bound ------------------------------------------------------------------------------------------------------------------
+def xlow(g, pk, shape, bits, wide):
+    """the operand of an 'xlow' case that holds the low pieces: integers with one element pinned to 2^bits - 1.  bf16x3: 12-bit values,
+    every 97th element `wide` bits (a non-zero third piece); 'xlow16': magnitudes <= 16 under the pinned one; else `bits` bits"""
+    top = 2 ** bits - 1
+    if pk == 'xlow16':
+        t = _ints(g, -16, 16, shape)
+    elif pk == 'bf16x3':
+        t = _ints(g, -4095, 4095, shape)
+        big = _ints(g, -(2 ** wide - 1), 2 ** wide - 1, shape)
+        t = torch.where((torch.arange(t.numel()) % 97 == 5).view(t.shape), big, t)
+    else:
+        t = _ints(g, -top, top, shape)
+    t.view(-1)[t.numel() // 2 + 3] = top
+    return t
+
+
+def wlow(g, shape, bits, wide):
+    """the operand of a 'wlow' case that holds the low pieces: `bits`-bit integers, every 61st of `wide` bits where wide is set"""
+    top = 2 ** bits - 1
+    t = _ints(g, -top, top, shape)
+    if wide:
+        big = _ints(g, -(2 ** wide - 1), 2 ** wide - 1, shape)
+        t = torch.where((torch.arange(t.numel()) % 61 == 7).view(t.shape), big, t)
+    return t
+
+
+def fold(which, N, G, H, W):
+    """dy of a 'fold' case: zero except in ONE source class, where the sources of every sum entry hold distinct integers"""
+    n_, k_, r_, q_ = torch.meshgrid(torch.arange(N), torch.arange(G), torch.arange(H), torch.arange(W), indexing='ij')
+    v = (1 + (5 * r_ + 3 * q_ + 7 * k_ + 11 * n_) % 59).float() * (1 - 2 * (k_ % 2)).float()
+    return v * fold_mask(which, H, W).view(1, 1, H, W).float()
+
+
 @functools.lru_cache(maxsize=None)
 def data(c):
     """(src, w, bias, addend, float64 reference BEFORE the activation and the addend, A, row exponents) of a case on the CPU: made once,
@@ -163,27 +196,13 @@ def data(c):
         b = _signed(g, M) if c.bias else None
         add = _signed(g, N, M, H, W) if c.add else None
     elif c.kind in ('xlow', 'xlow16'):
-        top = 2 ** c.bits - 1
-        if c.kind == 'xlow16':
-            src = _ints(g, -16, 16, (N, G, H, W))
-        elif c.pk == 'bf16x3':
-            src = _ints(g, -4095, 4095, (N, G, H, W))
-            wide = _ints(g, -(2 ** c.wide - 1), 2 ** c.wide - 1, (N, G, H, W))
-            pick = (torch.arange(src.numel()) % 97 == 5).view(src.shape)
-            src = torch.where(pick, wide, src)
-        else:
-            src = _ints(g, -top, top, (N, G, H, W))
-        src.view(-1)[src.numel() // 2 + 3] = top
+        src = xlow(g, 'xlow16' if c.kind == 'xlow16' else c.pk, (N, G, H, W), c.bits, c.wide)
         w = _ints(g, -1, 1, (K, C, 3, 3))
         b = _ints(g, -64, 64, (M,)) if c.bias else None
         add = _ints(g, -4096, 4096, (N, M, H, W)) if c.add else None
     elif c.kind == 'wlow':
-        top = 2 ** c.bits - 1
         src = _ints(g, -1, 1, (N, G, H, W))
-        w = _ints(g, -top, top, (K, C, 3, 3))
-        if c.wide:
-            wide = _ints(g, -(2 ** c.wide - 1), 2 ** c.wide - 1, (K, C, 3, 3))
-            w = torch.where((torch.arange(w.numel()) % 61 == 7).view(w.shape), wide, w)
+        w = wlow(g, (K, C, 3, 3), c.bits, c.wide)
         if c.pk == 'f16x2':
             rowexp = torch.randint(-20, 21, (M,), generator=g)
             rowexp[0], rowexp[1] = 20, -20
@@ -192,9 +211,7 @@ def data(c):
         assert not c.bias and not c.add
     else:
         assert c.kind == 'fold' and not fwd and not c.bias and not c.add
-        n_, k_, r_, q_ = torch.meshgrid(torch.arange(N), torch.arange(G), torch.arange(H), torch.arange(W), indexing='ij')
-        v = (1 + (5 * r_ + 3 * q_ + 7 * k_ + 11 * n_) % 59).float() * (1 - 2 * (k_ % 2)).float()
-        src = v * fold_mask(c.fold, H, W).view(1, 1, H, W).float()
+        src = fold(c.fold, N, G, H, W)
         w = _ints(g, -3, 3, (K, C, 3, 3))
     ref, A = reference(c, src, w, b)
     if add is not None:

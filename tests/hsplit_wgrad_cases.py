@@ -63,9 +63,9 @@ import functools
 
 import torch
 
-from oracle import ops_ref as R
 from conv_f32_cases import _signed
 from split_arith import U, cdiv, out_size, pow2_scale, split2h
+from split_arith import wgrad64 as grad64      # (float64 autograd of oracle.ops_ref.conv2d)
 
 TERM_MIN = 0.75 * 0.75
 F32, BF16 = 0, 1
@@ -416,13 +416,6 @@ D_SHAPES = (('gen', G(2, 16, 12, 32, 128, 4, 2, 1, Z), False), ('reflect', G(2, 
 
 
 # ---- data, reference, bounds ----------------------------------------------------------------------------------------------------------------
-def grad64(x, dy, geom):
-    N, C, H, W, K, Rr, S, st, pad, pm = geom
-    w = torch.zeros(K, C, Rr, S, dtype=torch.float64, requires_grad=True)
-    R.conv2d(x.double(), w, None, st, pad, pm).backward(dy.double())
-    return w.grad.detach()
-
-
 @functools.lru_cache(maxsize=None)
 def _data(geom, half, kind):
     N, C, H, W, K, Rr, S, st, pad, pm = geom

@@ -1,7 +1,7 @@
 """The arithmetic and the small helpers that the conv case tables share (tests/conv_f32_cases.py, hgemm_cases.py, halo_cases.py,
-thin_cases.py, hsplit_wgrad_cases.py): what csrc/common.h and csrc/bsplit.h hold once on the device side -- pow2_scale, split2h, split3,
+thin_cases.py, hsplit_wgrad_cases.py, bsplit_cases.py): what csrc/common.h and csrc/bsplit.h hold once on the device side -- pow2_scale, split2h, split3,
 the walk of thread_max_of_partials -- restated once in torch, so that the emulations can be held to float64 on the CPU; the float64
-reference of a forward / data-gradient call; and the scaling of the operand-range data.  A plain module, CPU only, no GPU and no library
+reference of a forward / data-gradient / weight-gradient call; and the scaling of the operand-range data.  A plain module, CPU only, no GPU and no library
 load; it imports no case module (they import it).  The bound derivations, the measured tables and the sensitivity studies stay in the
 docstrings of the case modules: nothing here is specific to one kernel."""
 import math
@@ -102,6 +102,14 @@ def reference(pass_, geom, src, w, b):
     f = _fwd64 if pass_ == 'fwd' else _dgrad64
     s64, w64, b64 = src.double(), w.double(), (b.double() if b is not None else None)
     return f(s64, w64, b64, geom), f(s64.abs(), w64.abs(), b64.abs() if b is not None else None, geom)
+
+
+def wgrad64(x, dy, geom):
+    """float64 weight gradient [K][C][R][S] of the convolution geom on (x, dy): autograd of oracle.ops_ref.conv2d"""
+    N, C, H, W, K, Rr, S, st, pad, pm = geom
+    w = torch.zeros(K, C, Rr, S, dtype=torch.float64, requires_grad=True)
+    R.conv2d(x.double(), w, None, st, pad, pm).backward(dy.double())
+    return w.grad.detach()
 
 
 def quanta(d):

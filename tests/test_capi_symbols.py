@@ -160,6 +160,27 @@ def test_hwgrad_launch_record_query():
     assert list(ig2) == list(ig) and list(wg2) == list(wg)
 
 
+def test_bsplit_launch_record_query():
+    """pcgan_bsplit_last_launch reads host memory only (callable without a GPU): entries past the record are 0, a null output and n <= 0
+    are refused, and it is a record of its own -- the query leaves the other three where they were"""
+    import ctypes
+    from pcgan_amd.hip import lib, ops
+    h = lib.load()
+    ig, wg, hw = (ctypes.c_int * 7)(), (ctypes.c_int * 9)(), (ctypes.c_int * 12)()
+    assert h.pcgan_igemm_last_launch(ig, 7) == 0 and h.pcgan_wgrad_last_launch(wg, 9) == 0 and h.pcgan_hwgrad_last_launch(hw, 12) == 0
+    buf = (ctypes.c_int * 13)(*([-1] * 13))
+    assert h.pcgan_bsplit_last_launch(buf, 13) == 0 and list(buf)[11:] == [0, 0] and min(buf) >= 0
+    short = (ctypes.c_int * 3)(*([-1] * 3))
+    assert h.pcgan_bsplit_last_launch(short, 2) == 0 and list(short)[:2] == list(buf)[:2] and short[2] == -1
+    assert h.pcgan_bsplit_last_launch(None, 11) != 0 and b'bsplit_last_launch' in h.pcgan_last_error()
+    assert h.pcgan_bsplit_last_launch(buf, 0) != 0 and h.pcgan_bsplit_last_launch(buf, -1) != 0
+    rec = ops.bsplit_last_launch()
+    assert tuple(rec) == ops.BSPLIT_FIELDS and len(rec) == 11 and rec['seq'] == buf[0]
+    ig2, wg2, hw2 = (ctypes.c_int * 7)(), (ctypes.c_int * 9)(), (ctypes.c_int * 12)()
+    assert h.pcgan_igemm_last_launch(ig2, 7) == 0 and h.pcgan_wgrad_last_launch(wg2, 9) == 0 and h.pcgan_hwgrad_last_launch(hw2, 12) == 0
+    assert list(ig2) == list(ig) and list(wg2) == list(wg) and list(hw2) == list(hw)
+
+
 def test_forced_hwgrad_splits_size_the_workspace():
     """option "hwgrad_ks" (host arithmetic only): pcgan_conv2d_hsplit_wgrad_workspace_bytes holds exactly the forced number of partial
     sums, cut to the number of 16-column stages, behind the padded copy where there is one; 0 gives the heuristic's size back"""

@@ -142,6 +142,9 @@ class _Call(object):
         else:
             assert add is None and maxima is None and b is None and act == 0
             L.check(lib.pcgan_conv2d_bwd_data_bsplit(ref, ptr(src), ptr(self.pk), ptr(y), self.st), 'conv2d_bwd_data_bsplit')
+        if c.pk != 'f16x2':      # the launch record of the bsplit entries: the window kernel, not the per-tap one
+            rec = ops.bsplit_last_launch()
+            assert (rec['kernel'], rec['mode'], rec['bm']) == (1, 0 if c.pass_ == 'fwd' else 1, 256), rec
         torch.cuda.synchronize()
         assert bool((big[:GUARD] == 0xFF).all()) and bool((big[GUARD + nbytes:] == 0xFF).all()), 'the call wrote outside its output'
         assert bool((self.pk[self.nb:] == 0xFF).all()), 'the pack wrote behind the %d bytes it asked for' % self.nb
